@@ -6,7 +6,9 @@ at batch B, CFG combine, DPM-Solver++ update.  Workload (BASELINE.json configs[1
 with PhotoVerse cross-attention processors, B=16 per GPU, 64x64 latents (512x512), fp16 storage / fp32 accumulate,
 synthetic conditioning.  N>1: one process per GPU, batch sharded (weak scaling), one all_gather of the final latents.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).  A plain run sets up, warms up, times the steps and prints
+the headline; `--full` adds every separately labelled measurement (roofline, xattn_fused, shared_prefix, ip_tokens_5,
+configs4_per_rank, train_forward, train_step, cpu_baseline).  `--dump-outputs DIR` writes the latents of the last timed step.
 """
 import argparse
 import json
@@ -25,6 +27,8 @@ MFMA_PEAK_TFLOPS = 2500.0   # dense fp16 MFMA peak, MI355X_MICROARCH.md "Chip-le
 #: kernel sources it was measured on; bench.py reports `traffic_stale` when those differ from the sources in the tree)
 PMC_TRAFFIC_FILE = "profiles/r06_pmc_traffic.json"
 KERNEL_SOURCES = ("photoverse_amd/csrc/pv_gemm.hip", "photoverse_amd/csrc/pv_convbig.hip", "photoverse_amd/csrc/pv_attn.hip")
+#: size cap of --dump-outputs; a larger output is written as a fixed, seeded sample of its elements
+DUMP_MAX_BYTES = 64 << 20
 
 
 def git_blob_sha1(path):
@@ -330,12 +334,19 @@ def main():
     ap.add_argument("--batch-splits", type=int, default=1, help="independent sub-batches per forward (extra parallel graph branches)")
     ap.add_argument("--one-stream", action="store_true",
                     help="run the uncond / cond forwards back to back on one stream instead of as two parallel graph branches")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the separately labelled measurements too (roofline, xattn_fused, shared_prefix, ip_tokens_5, "
+                         "configs4_per_rank, train_forward, train_step, cpu_baseline); the --no-* options below trim them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-train-forward", action="store_true", help="skip the separately labelled training-shaped forward measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the gathered latents after the last timed step as DIR/latents.npy (float32; seeded inputs: identical from run to run)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher self-test (no GPU): every rank reports its RANK / WORLD_SIZE and exits")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- launch: N ranks, one per GPU --------------------------------------------------------------------------
     # Under an external launcher (torch.distributed.run sets RANK / WORLD_SIZE) this process IS one rank; otherwise the
@@ -432,6 +443,13 @@ def main():
         dt = max(t.item() for t in allt)
     rccl_world = dist.get_world_size() if use_dist else 1
     finite = bool(torch.isfinite(final).all().item())
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        arr = final.float().cpu().numpy()
+        if arr.nbytes > DUMP_MAX_BYTES:
+            arr = arr.reshape(-1)[np.sort(np.random.default_rng(0).choice(arr.size, DUMP_MAX_BYTES // 4, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), arr)
 
     def replay(groups, reps=5):
         """``groups``: one after the other; a group is a list of LANES, a lane a list of recorders run in order on one stream: lane 0 on the current
@@ -471,7 +489,7 @@ def main():
         return [[lane_u, lane_c]] + alone
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # dominant kernel = the launch SYMBOL with the largest share of one step's algorithmic flops.  Rounds 1-4 that was the 3x3 conv on the big tile
         # (25 % of a step's flops under one symbol); since round 5 the 64 x 64 convs run on the LDS-resident-patch instantiation (MODE 3, 13.2 %) and the
         # 32 x 32 convs stay on the gathered one (MODE 0, 12.2 %), so the largest single symbol is the d = 40 self-attention kernel attn8_kernel<497>
@@ -543,7 +561,7 @@ def main():
     # in the step's schedule (the uncond and cond plans side by side on two streams, the merged low-resolution plan alone) between HIP events.  (The text / image-token K, V projections depend on the conditioning only and run
     # once per generation, outside the step.)
     xfused = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         levels, tot_ms, tot_fl, tot_n = {}, 0.0, 0.0, 0
         for C_ in (320, 640, 1280):
             subs = [e.rec.subset_role(f"attn2:{C_}") for e in loop.all_engines]
@@ -576,7 +594,7 @@ def main():
     # OPTIONAL, separately labelled (round-3 verdict item 9): the two CFG forwards of a step share the part that never sees the conditioning (conv_in ->
     # first ResnetBlock -> first transformer block up to attn1): exact (bit-identical latents), 2.5 % fewer flops.  `value` above stays two FULL forwards.
     shared = None
-    if rank == 0 and world == 1 and not args.no_roofline and not args.one_stream and args.batch_splits == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and not args.one_stream and args.batch_splits == 1:
         k2 = min(args.steps, 20)
         loop2 = DenoiseLoop(unet, B, S, P, max(k2, 3), args.guidance, use_graph=not args.no_graph, share_prefix=True)
         if loop2.share_prefix:
@@ -607,7 +625,7 @@ def main():
     # Inference-style engine (fused GEGLU / fused attn2, no activations kept); the whole iteration is `train_step` below.  NOT part of `value`.
     train_fwd = ip5 = cfg4 = None
     launches_per_step = loop.launches_per_step
-    if rank == 0 and world == 1 and not args.no_train_forward and S == 64:
+    if args.full and rank == 0 and world == 1 and not args.no_train_forward and S == 64:
         loop = subs = None          # release the loop's ~8 GB of static buffers before building the training-shaped engine
         torch.cuda.empty_cache()
         set_visual_cross_attention_adapter(unet, (5,))
@@ -696,13 +714,13 @@ def main():
     # adapters + text encoder + UNet forward, the backward through all of them, per-module gradient clipping and AdamW - as two
     # replayed launch plans (photoverse_amd/train.py TrainStep).  NOT part of `value`.
     train_step = None
-    if rank == 0 and world == 1 and not args.no_train_forward and S == 64:
+    if args.full and rank == 0 and world == 1 and not args.no_train_forward and S == 64:
         eng = gr = None
         torch.cuda.empty_cache()
         train_step = train_step_leg(unet, B, S, dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported at N = 1 only (contract); N > 1 runs stay short
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported at N = 1 only (contract); N > 1 runs stay short
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -722,6 +740,7 @@ def main():
             "finite": finite, "rccl_world": rccl_world, "collective": ("all_gather_into_tensor over RCCL (final latents)" if use_dist else "none (single process)"),
             "ms_per_step_ranks": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3), "n": len(rank_ms)},
             "step_mfma_frac": (round(step_tflop / (dt / args.steps) / 1e0 / MFMA_PEAK_TFLOPS, 4) if step_tflop else None),
+            "full": args.full,          # without --full the separately labelled objects below are null (not measured)
             "roofline": roofline, "xattn_fused": xfused, "shared_prefix": shared, "ip_tokens_5": ip5, "configs4_per_rank": cfg4, "train_forward": train_fwd, "train_step": train_step, "cpu_baseline": cpu,
         }
         print(json.dumps(out))

@@ -527,7 +527,7 @@ def test_sharded_pipeline_seeded_noise_equals_one_rank_draw_gloo_world2():
 
 def test_bench_self_launches_n_ranks_dry():
     """`python bench.py --gpus N` spawns N ranks itself (no torchrun): distinct ranks / processes, n_gpus == world size;
-    with no GPUs it fails cleanly; a mismatching external launcher is refused."""
+    with no GPUs it fails cleanly; a mismatching external launcher and a run of no timed steps are refused."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
@@ -543,6 +543,8 @@ def test_bench_self_launches_n_ranks_dry():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch"], capture_output=True, text=True,
                        env=dict(env, RANK="0", WORLD_SIZE="1"), timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and r.stdout.strip() == ""
 
 
 def test_bench_dry_launch_at_the_real_world_size_and_workload_labels():

@@ -28,7 +28,9 @@ def test_adapter_matches_real_reference(golden_dir):
         for key, ti in (("none", None), ("full", "full"), ("0", 0), ("1", 1)):
             out = ad(embs, token_index=ti)
             assert out.shape == g["outs"][key].shape
-            torch.testing.assert_close(out, g["outs"][key], rtol=0, atol=0)
+            # bit-identical where the CPU BLAS takes the fixture host's kernel path; a host whose BLAS takes another one (no AVX-512,
+            # another vendor) sums the K = 1024 products in another order: measured 7e-7 max abs (rel-L2 4e-7), bound 32 ulp of max |out|
+            torch.testing.assert_close(out, g["outs"][key], rtol=0, atol=32 * torch.finfo(torch.float32).eps * g["outs"][key].abs().max().item())
     # adapters.py:32-37: integer token_index returns (B,1,768) == column of the full output
     assert torch.equal(g["outs"]["0"], g["outs"]["full"][:, :1])
 

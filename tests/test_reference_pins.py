@@ -96,9 +96,17 @@ def test_processor_matches_reference_call(golden_dir, P):
 
         def gr(v):
             return torch.zeros_like(v) if v.grad is None else v.grad
-        for got, exp in ((gr(h), e["d_hs"]), (gr(t)[:, :, ::8], e["d_text"]), (gr(i), e["d_ip"]), (gr(ps[0])[::4, ::4], e["d_to_k_ip"]),
-                         (gr(ps[1])[::4, ::4], e["d_to_v_ip"])):
-            assert (got - exp).norm() <= 2e-5 * exp.norm() + 1e-6
+        pairs = ((gr(h), e["d_hs"]), (gr(t)[:, :, ::8], e["d_text"]), (gr(i), e["d_ip"]), (gr(ps[0])[::4, ::4], e["d_to_k_ip"]),
+                 (gr(ps[1])[::4, ::4], e["d_to_v_ip"]))
+        # a gradient that vanishes in exact arithmetic (P = 1: the image-token softmax has one key, its weight is 1 whatever K is, so nothing
+        # reaches to_k_ip, nor hs in the image-only branch) is fp32 rounding noise, ~1e-7 of the case's largest gradient, and that noise
+        # depends on the host's BLAS kernels: it must vanish here too.  Every other gradient matches the fixture to 2e-5.
+        scale = max(exp.norm() for _, exp in pairs)
+        for got, exp in pairs:
+            if exp.norm() <= 1e-6 * scale:
+                assert got.norm() <= 1e-6 * scale
+            else:
+                assert (got - exp).norm() <= 2e-5 * exp.norm() + 1e-6
     # the three regions really are different branches
     assert not torch.allclose(c["grad_text"]["out"], c["grad_sum"]["out"]) and not torch.allclose(c["grad_ip"]["out"], c["grad_sum"]["out"])
 

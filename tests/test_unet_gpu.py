@@ -276,16 +276,18 @@ def test_fifty_step_loop_latent_tolerance(tiny_pair, golden_dir):
     assert err < 1.5e-3          # measured 7.9e-4 .. 8.1e-4 on MI355X (north_star target 1e-3); headroom for fp32 summation-order variation
 
 
-def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the driver's contract keys plus the roofline object (short run, no CPU baseline)."""
+def test_bench_contract_line(tmp_path):
+    """bench.py prints ONE JSON line with the driver's contract keys plus, under --full, the roofline object (short run, no CPU baseline);
+    a plain run leaves the separately labelled objects null and --dump-outputs writes the latents of its last timed step."""
     import json
     import os
     import subprocess
     import sys
+    import numpy as np
     if not torch.cuda.is_available():
         pytest.skip("needs a HIP device")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -321,10 +323,16 @@ def test_bench_contract_line():
     sp = d["shared_prefix"]
     assert sp["what"].startswith("NOT the headline") and 0.97 < sp["flops_vs_two_full_forwards"] < 0.98 and sp["launches_per_step"] < d["config"]["launches_per_step"]
     assert sp["value"] > 0.9 * d["value"]
-    r2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-roofline",
-                         "--no-train-forward"], capture_output=True, text=True, timeout=600, cwd=root)
+    r2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r2.returncode == 0, r2.stderr[-2000:]
-    assert json.loads([l for l in r2.stdout.splitlines() if l.startswith("{")][0])["config"]["workload"].startswith("custom shape (NOT a BASELINE config)")
+    d2 = json.loads([l for l in r2.stdout.splitlines() if l.startswith("{")][0])
+    assert d2["config"]["workload"].startswith("custom shape (NOT a BASELINE config)")
+    assert d2["full"] is False and d2["steps"] == 2 and d2["ms_per_step"] > 0
+    for k in ("roofline", "xattn_fused", "shared_prefix", "ip_tokens_5", "configs4_per_rank", "train_forward", "train_step", "cpu_baseline"):
+        assert d2[k] is None, k
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (2, 4, 64, 64) and np.isfinite(lat).all() and lat.std() > 0
 
 
 def test_bench_under_torch_distributed_run_uses_rccl_and_agrees_with_the_plain_run():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Profile bench.py on the GPU box: (1) rocprofv3 --kernel-trace --stats, (2) PMC passes (counters only, separate
-runs as MI355X_MICROARCH.md prescribes) for HBM traffic of the dominant kernel.  Writes summaries under gpurun_out/prof_bench/
+runs as MI355X_MICROARCH.md prescribes) for HBM traffic of the dominant kernel.  Writes summaries under $PV_PROFILE_OUT/prof_bench/ (default profile_out/)
 (copy the ones to keep into profiles/).  Usage: python3 tools/profile_bench.py [steps]"""
 import csv
 import glob
@@ -11,12 +11,12 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out", "prof_bench")
+OUT = os.path.join(os.path.abspath(os.environ.get("PV_PROFILE_OUT", os.path.join(ROOT, "profile_out"))), "prof_bench")
 steps = sys.argv[1] if len(sys.argv) > 1 else "5"
 sys.path.insert(0, ROOT)
 from bench import KERNEL_SOURCES, git_blob_sha1  # noqa: E402
 env = dict(os.environ, TMPDIR="/tmp")
-base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "2", "--no-cpu-baseline", "--no-train-forward"]
+base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "2", "--full", "--no-cpu-baseline", "--no-train-forward"]
 
 
 def run(args, tag):
