@@ -1,0 +1,907 @@
+"""fp64 references of the C-ABI launchers, computed from a launch's own parameter block (``include/photoverse_hip.h``).
+
+Each launcher has two functions here:
+
+* ``LAYOUT[name](p)`` - the buffers the parameter block ``p`` addresses: field -> ``Buf(dtype, rows, cols, ld, role)``.  ``role`` is ``"in"``,
+  ``"out"``, ``"inout"`` (read and written in place), ``"scratch"`` (written, contents undefined) or ``"opaque"`` (an output whose layout the
+  header leaves undocumented: checked for determinism only, and through its consumer).
+* ``REF[name](p, v)`` - ``v`` maps every non-NULL field to a 2-D ``[rows, cols]`` view of its buffer; the result maps each checked output
+  field to an ``Expect``: the fp64 reference, a per-element error bound, and the aggregate term of its documented intermediates.
+
+The semantics are written from the header alone.  Arithmetic is fp64 on the exact fp16 / fp32 inputs, with plain ``torch.matmul``; a 3x3
+convolution is nine shifted matmuls.  Error bounds (every constant derived here, none fitted to a measurement):
+
+* ``U16 = 2^-11``: half an fp16 ulp, the relative error of rounding a normal value to fp16; ``SUB16 = 2^-25``: half the fp16 subnormal spacing,
+  its absolute error below 2^-14.  The final fp16 store is allowed ``2^-10 |ref| + 2^-24`` (twice that: the store rounds ``ref + e``, not ``ref``).
+* ``U32 = 2^-24``: the same for fp32.
+* ``mfma_c(K)``: fp16 products are exact in fp32 and the MFMA accumulates them as a k-ordered fp32 chain; the CDNA guide measures that chain
+  against fp64 at 0.75-1.5e-7 Sum|a b| for K <= 1024 and 3.5e-7 Sum|a b| at K = 4096.  A chain's worst error grows linearly in its length, so
+  ``c(K) = 3.5e-7 max(1, K / 4096)``.
+* ``gamma(n) = n U32``: worst relative error of an n-term fp32 sum of same-sign values (norm statistics, softmax normalisers).
+* ``DACT = 1.13``: the largest slope of SiLU / quick-GELU / GELU / LeakyReLU (GELU's is 1.129), the factor an accumulator error passes through
+  an activation with.
+* ``GELU_APPROX = 1.25e-5``: the documented absolute error bound of the epilogues' erf approximation, per unit |x| (``pv_common.h``).
+
+Two kinds of error term.  ``det``: worst-case terms (accumulation, the erf approximation, norm statistics), added as they are.  ``sig``: the
+documented fp16 roundings of intermediates (q, P, the normalised rows, the attention context).  Each is an independent rounding bounded by
++-U16 |t|, so a sum of many of them through a linear stage adds in quadrature: ``sig = sqrt(Sum (U16 t_j w_j)^2)``, a standard deviation
+bounded with the largest rounding (the uniform rounding's is U16 |t| / sqrt 3).  Summing them with absolute values instead grows with
+sqrt(terms) faster than the error does and would let an O(1e-2) error pass.
+* Element bound: ``store + det + KAPPA sig``, ``KAPPA = 6`` (with the sqrt 3 above, more than 10 standard deviations).
+* Aggregate bound: ``1.5 rel_l2(round(ref), ref) + 1e-6 + (||det|| + 2 ||sig||) / ||ref||`` (twice the expected rms of the statistical
+  part), and never looser than the tolerance ``tests/test_hip_kernels.py`` asserts for the same launcher (``CAP``).
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Callable, Dict, Optional
+
+import torch
+
+F16, F32, I32 = torch.float16, torch.float32, torch.int32
+U16, SUB16, U32 = 2.0 ** -11, 2.0 ** -25, 2.0 ** -24
+STORE16_REL, STORE16_ABS = 2.0 ** -10, 2.0 ** -24
+STORE32_REL = 2.0 ** -23
+DACT = 1.13
+GELU_APPROX = 1.25e-5
+LN2 = math.log(2.0)
+KAPPA = 6.0
+
+#: aggregate rel-L2 tolerances the kernel tests assert for each launcher (tests/test_hip_kernels.py): no audit bound is looser
+CAP = {"gemm16": 1e-3, "gemm32": 2e-5, "attention": 2e-3, "xattn": 2e-3, "lnq": 2e-3, "fused": 1e-3, "fused_attn": 3e-3, "row_gemm": 1e-3,
+       "layernorm": 1e-3, "groupnorm": 1e-3, "conv_out": 1e-5}
+
+
+def mfma_c(k: int) -> float:
+    return 3.5e-7 * max(1.0, k / 4096.0)
+
+
+def gamma(n: int) -> float:
+    return n * U32
+
+
+@dataclass
+class Buf:
+    dtype: torch.dtype
+    rows: int
+    cols: int
+    ld: int
+    role: str = "in"
+
+
+@dataclass
+class Expect:
+    ref: torch.Tensor                 # fp64, the shape of the output view
+    bound: torch.Tensor               # fp64, per element
+    agg_extra: float = 0.0            # aggregate (rel-L2) allowance of documented intermediates
+    store: Optional[torch.dtype] = None   # the output type: the aggregate bound rounds ``ref`` to it; None = exact (bit compare)
+    after: Optional[Callable] = None  # after(got_views) -> Expect: a check that needs the kernel's own output (column statistics)
+    cap: Optional[float] = None       # the aggregate bound never exceeds this (CAP)
+    derive: Optional[Callable] = None  # derive(got_views) -> the tensor compared (default: the field itself)
+    rounded: Optional[torch.Tensor] = None   # the exact answer as stored (default: ref rounded to ``store``), for the aggregate bound
+
+
+def f64(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.float64)
+
+
+def store_bound(ref: torch.Tensor, dtype) -> torch.Tensor:
+    if dtype == F16:
+        return STORE16_REL * ref.abs() + STORE16_ABS
+    return STORE32_REL * ref.abs() + 2.0 ** -140
+
+
+def expect(ref, det, dtype, sig=None, cap=None):
+    """Element bound = store rounding + ``det`` + KAPPA ``sig``; aggregate allowance (||det|| + 2 ||sig||) / ||ref||, capped at ``cap``."""
+    den = ref.norm().item()
+    tot = det.norm().item() + (0.0 if sig is None else 2 * sig.norm().item())
+    bound = store_bound(ref, dtype) + det + (0.0 if sig is None else KAPPA * sig)
+    return Expect(ref, bound, (tot / den) if den > 0 else 0.0, dtype, cap=cap)
+
+
+def _act(x, act):
+    if act == 0:
+        return x
+    if act == 1:
+        return x * torch.sigmoid(x)
+    if act == 2:
+        return x * torch.sigmoid(1.702 * x)
+    if act == 3:
+        return torch.where(x > 0, x, 0.01 * x)
+    if act == 4:
+        return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+    raise ValueError(f"unknown activation {act}")
+
+
+def _gelu(x):
+    return _act(x, 4)
+
+
+def _ptr(p, name) -> bool:
+    return bool(getattr(p, name))
+
+
+# ===================================================================================================================== pv_gemm_conv
+def gemm_geometry(p):
+    """(images, rows per image) of the epilogue's ``rowadd`` indexing and the input row count."""
+    if p.taps == 9:
+        return p.batch, p.hout * p.wout, p.batch * p.hin * p.win
+    rpi = p.hout * p.wout
+    return (p.M + rpi - 1) // rpi, rpi, p.M
+
+
+def gemm_unpack_geglu(N: int):
+    """Packed weight row -> (output column, is gate), from ``pack_geglu``'s documented fragment order: each 128-row tile holds, per wave
+    half, alternating 16-row [value | gate] fragments of the same 16 output columns."""
+    pr = torch.arange(N)
+    t, wn, ni, e = pr // 128, (pr % 128) // 64, (pr % 64) // 16, pr % 16
+    return t * 64 + wn * 32 + (ni // 2) * 16 + e, (ni & 1).bool()
+
+
+def rowgemm_unpack_geglu(N: int):
+    """``pv_row_gemm``'s order: per 160-row chunk c, fragment 2q = value rows of columns 80 c + 16 q .., fragment 2q + 1 = their gate rows."""
+    pr = torch.arange(N)
+    c, i, e = pr // 160, (pr % 160) // 16, pr % 16
+    return 80 * c + 16 * (i // 2) + e, (i & 1).bool()
+
+
+def layout_gemm(p):
+    imgs, rpi, rows_in = gemm_geometry(p)
+    n_out = p.N // 2 if p.geglu else p.N
+    L = {"a0": Buf(F16, rows_in, p.c0, p.lda0), "w": Buf(F16, p.N, p.taps * (p.c0 + p.c1), p.taps * (p.c0 + p.c1)),
+         "out": Buf(F32 if p.out_f32 else F16, p.M, n_out, p.ldc, "out")}
+    if _ptr(p, "a1"):
+        L["a1"] = Buf(F16, rows_in, p.c1, p.lda1)
+    if _ptr(p, "bias"):
+        L["bias"] = Buf(F32, 1, p.N, p.N)
+    if _ptr(p, "rowadd"):
+        L["rowadd"] = Buf(F32, imgs if p.rowadd_ld else 1, n_out, p.rowadd_ld or n_out)
+    if _ptr(p, "residual"):
+        L["residual"] = Buf(F16, p.M, n_out, p.ldr)
+    if p.splitk > 1 and _ptr(p, "splitk_ws"):
+        L["splitk_ws"] = Buf(F32, p.splitk * p.M, p.N, p.N, "scratch")
+    if _ptr(p, "colstats"):
+        L["colstats"] = Buf(F32, (p.M + 63) // 64, 2 * n_out, 2 * n_out, "out")
+    if _ptr(p, "ln_rowsum"):
+        L["ln_rowsum"] = Buf(F32, 1, p.N, p.N)
+    if _ptr(p, "a_norm"):
+        L["a_norm"] = Buf(F32, p.batch, 2 * (p.c0 + p.c1), 2 * (p.c0 + p.c1))
+    return L
+
+
+def conv_taps(x: torch.Tensor, batch, hin, win, hout, wout, stride, upsample, pad):
+    """The nine shifted input matrices of a 3x3 conv over NHWC rows x [batch*hin*win, C]: tap t = 3 ky + kx -> [batch*hout*wout, C].
+    Logical input = the x2 nearest upsample when ``upsample``; zero padding ``pad`` in front; reads past the bottom / right edge are 0."""
+    C = x.shape[1]
+    img = x.reshape(batch, hin, win, C)
+    if upsample:
+        img = img.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    hl, wl = img.shape[1], img.shape[2]
+    need_h, need_w = (hout - 1) * stride + 3, (wout - 1) * stride + 3
+    padded = img.new_zeros(batch, max(need_h, hl + pad), max(need_w, wl + pad), C)
+    padded[:, pad:pad + hl, pad:pad + wl] = img
+    out = []
+    for ky in range(3):
+        for kx in range(3):
+            out.append(padded[:, ky:ky + (hout - 1) * stride + 1:stride, kx:kx + (wout - 1) * stride + 1:stride].reshape(-1, C))
+    return out
+
+
+def ref_gemm(p, v):
+    imgs, rpi, rows_in = gemm_geometry(p)
+    K1 = p.c0 + p.c1
+    a = f64(v["a0"]) if p.c1 == 0 else torch.cat([f64(v["a0"]), f64(v["a1"])], 1)
+    sig2 = None
+    if "a_norm" in v:
+        # GroupNorm folded into the conv: per image and input channel scale / shift, act, then the fp16 rounding pv_groupnorm_apply does
+        tab = f64(v["a_norm"]).reshape(p.batch, 2, K1)
+        img = torch.arange(rows_in, device=a.device) // (p.hin * p.win)
+        a = _act(a * tab[img, 0] + tab[img, 1], p.a_norm_act)
+        a = a.to(F16).to(torch.float64)     # the kernel rounds the same fp32 value: a rare one-ulp flip, at most U16 |a| per element
+        sig2 = 0
+    w = f64(v["w"])
+    if p.taps == 9:
+        xs = conv_taps(a, p.batch, p.hin, p.win, p.hout, p.wout, p.stride, p.upsample, p.pad)
+        acc = torch.zeros(p.M, p.N, dtype=torch.float64, device=a.device)
+        S = torch.zeros_like(acc)
+        for t, xt in enumerate(xs):
+            wt = w[:, t * K1:(t + 1) * K1]
+            acc += xt @ wt.T
+            S += xt.abs() @ wt.abs().T
+            if sig2 is not None:
+                sig2 = sig2 + (U16 * xt) ** 2 @ (wt * wt).T
+    else:
+        acc = a @ w.T
+        S = a.abs() @ w.abs().T
+        if sig2 is not None:
+            sig2 = (U16 * a) ** 2 @ (w * w).T
+    Kt = p.taps * K1
+    err = mfma_c(Kt) * S
+    sig = None if sig2 is None else torch.sqrt(sig2)
+    if "ln_rowsum" in v:
+        # LayerNorm folded into the GEMM: epilogue rstd * (acc - mean * rowsum[n]) over the raw rows of a0 (K = c0)
+        x = f64(v["a0"])
+        mean = x.mean(1, keepdim=True)
+        var = ((x - mean) ** 2).mean(1, keepdim=True)
+        rstd = 1.0 / torch.sqrt(var + float(p.ln_eps))
+        rs = f64(v["ln_rowsum"]).reshape(1, -1)
+        acc = rstd * (acc - mean * rs)
+        # accumulation of both terms, then the row statistics' fp32 sums (relative gamma(K) on mean and variance -> on the result)
+        err = rstd * (err + mfma_c(Kt) * mean.abs() * rs.abs()) + 2 * gamma(p.c0) * acc.abs() + rstd * gamma(p.c0) * x.abs().mean(1, keepdim=True) * rs.abs()
+    if "bias" in v:
+        acc = acc + f64(v["bias"]).reshape(1, -1)
+    n_out = p.N // 2 if p.geglu else p.N
+    rows = torch.arange(p.M, device=acc.device)
+    if p.geglu:
+        col, gate = gemm_unpack_geglu(p.N)
+        col, gate = col.to(acc.device), gate.to(acc.device)
+        val = torch.empty(p.M, n_out, dtype=torch.float64, device=acc.device)
+        gt, ev, eg = torch.empty_like(val), torch.empty_like(val), torch.empty_like(val)
+        val[:, col[~gate]] = acc[:, ~gate]
+        gt[:, col[gate]] = acc[:, gate]
+        ev[:, col[~gate]] = err[:, ~gate]
+        eg[:, col[gate]] = err[:, gate]
+        g = _gelu(gt)
+        acc = val * g
+        # value error x |gelu(gate)| + |value| x gelu slope x gate error + the erf approximation (GEGLU: one fp16 rounding of the fp32 product)
+        err = ev * g.abs() + val.abs() * (DACT * eg + GELU_APPROX * gt.abs())
+        if sig is not None:
+            sv, sg = torch.empty_like(val), torch.empty_like(val)
+            sv[:, col[~gate]], sg[:, col[gate]] = sig[:, ~gate], sig[:, gate]
+            sig = torch.sqrt((sv * g) ** 2 + (DACT * val * sg) ** 2)
+    if "rowadd" in v:
+        ra = f64(v["rowadd"])
+        acc = acc + (ra[rows // rpi] if p.rowadd_ld else ra.reshape(1, -1))
+    if p.act:
+        acc = _act(acc, p.act)
+        err = DACT * err
+        sig = None if sig is None else DACT * sig
+    if "residual" in v:
+        acc = acc + f64(v["residual"])
+    dt = F32 if p.out_f32 else F16
+    res = {"out": expect(acc, err, dt, sig, CAP["gemm32" if p.out_f32 else "gemm16"])}
+    if "colstats" in v:
+        res["colstats"] = Expect(None, None, 0.0, F32, after=lambda got, M=p.M, n=n_out: colstats_expect(got["out"], M, n))
+    return res
+
+
+def colstats_expect(y: torch.Tensor, M: int, N: int) -> Expect:
+    """Per 64-row block and column: (sum, sum of squares) of the kernel's OWN fp16 output; fp32 accumulation of <= 64 terms: gamma(64)."""
+    yy = f64(y)
+    nb = (M + 63) // 64
+    pad = torch.zeros(nb * 64 - M, N, dtype=torch.float64, device=yy.device)
+    blk = torch.cat([yy, pad]).reshape(nb, 64, N)
+    s, ss = blk.sum(1), (blk * blk).sum(1)
+    sa = blk.abs().sum(1)
+    ref = torch.stack([s, ss], 1).reshape(nb, 2 * N)
+    bound = torch.stack([gamma(64) * sa, gamma(64) * ss], 1).reshape(nb, 2 * N) + 2.0 ** -140
+    return Expect(ref, bound, 0.0, F32)
+
+
+# ===================================================================================================================== attention
+def sdpa(q, k, v, scale, causal=False, q_sig=None, q_det=None):
+    """softmax(q k^T scale) v over [..., n, d] (leading dims batched) in fp64, with its error terms: (out, lse, det, sig).
+
+    First-order effects of each perturbation on out_i = Sum_j p_ij v_j:
+    - a score error e_ij moves out_i by Sum_j p_ij e_ij (v_j - out_i).  Per score: the fp32 accumulation of its d products (mfma_c(d) |q|.|k_j|
+      scale) and the fp32 rounding of the exp2 argument (2 U32 (|s_ij| + |max_j s_ij|)); independent across (i, j): quadrature.
+    - a q error dq moves out_i by scale Sum_d dq_d Cov_p(v, k_d) (the p_i-weighted covariance of v and column d of k).  q's fp16 rounding
+      (the kernels fold scale log2 e into q once; lnq / fused pass their q stage as ``q_sig``), independent across d: quadrature; ``q_det``:
+      worst case.
+    - P rounded to fp16 for the PV product, and exp2's own ulp: (U16 + 2 U32) p_ij v_j, independent across j: quadrature.
+    - the normaliser, an nk-term fp32 sum: a random walk of sqrt(nk) U32 relative, scaling out_i.
+    - the PV accumulation: mfma_c(nk) Sum_j p_ij |v_j| (det)."""
+    nk, d = k.shape[-2], k.shape[-1]
+    s = (q @ k.transpose(-1, -2)) * scale
+    qk = (q.abs() @ k.abs().transpose(-1, -2)) * scale
+    if causal:
+        i = torch.arange(q.shape[-2], device=q.device)[:, None]
+        j = torch.arange(nk, device=q.device)[None, :]
+        s = s.masked_fill(j > i, float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse[..., None])
+    out = p @ v
+    sf = torch.where(torch.isfinite(s), s, torch.zeros_like(s))
+    e = mfma_c(d) * qk + 2 * U32 * (sf.abs() + sf.abs().amax(-1, keepdim=True))
+    A = (p * e) ** 2
+    var = (A @ (v * v) - 2 * out * (A @ v) + out ** 2 * A.sum(-1, keepdim=True)).clamp_min(0)
+    var = var + ((U16 + 2 * U32) * p) ** 2 @ (v * v) + (math.sqrt(nk) * U32 * out) ** 2
+    vk = (v.unsqueeze(-1) * k.unsqueeze(-2)).reshape(*v.shape[:-1], v.shape[-1] * d)
+    cov = (p @ vk).reshape(*out.shape, d) - out.unsqueeze(-1) * (p @ k).unsqueeze(-2)
+    qs = U16 * q.abs() if q_sig is None else q_sig
+    var = var + torch.einsum("...id,...icd->...ic", (scale * qs) ** 2, cov * cov)
+    det = mfma_c(nk) * (p @ v.abs())
+    if q_det is not None:
+        det = det + torch.einsum("...id,...icd->...ic", scale * q_det, cov.abs())
+    # log-sum-exp (natural units): the largest score error, the q rounding through |k|, the normaliser and the log / exp ulps
+    lerr = ((mfma_c(d) + U16) * qk).amax(-1) + math.sqrt(nk) * U32 * KAPPA + 4 * U32
+    return out, lse, det, torch.sqrt(var), lerr
+
+
+def layout_attention(p):
+    C = p.heads * p.d
+    L = {"q": Buf(F16, p.batch * p.nq, C, p.ldq), "k": Buf(F16, p.batch * p.nk, C, p.ldk), "v": Buf(F16, p.batch * p.nk, C, p.ldv),
+         "out": Buf(F16, p.batch * p.nq, C, p.ldo, "out")}
+    if _ptr(p, "lse"):
+        L["lse"] = Buf(F32, p.batch * p.heads, p.nq, p.nq, "out")
+    return L
+
+
+def ref_attention(p, v):
+    B, H, nq, nk, d = p.batch, p.heads, p.nq, p.nk, p.d
+    scale = 1.0 / math.sqrt(d)
+    q, k, vv = f64(v["q"]), f64(v["k"]), f64(v["v"])
+    out = torch.empty(B * nq, H * d, dtype=torch.float64, device=q.device)
+    det, sig = torch.empty_like(out), torch.empty_like(out)
+    lse = torch.empty(B * H, nq, dtype=torch.float64, device=q.device)
+    lerr = torch.empty_like(lse)
+    for b in range(B):                      # one (image, head) at a time: the score matrix of a 96 x 96 latent is 9216^2
+        for h in range(H):
+            r, c = slice(b * nq, (b + 1) * nq), slice(h * d, (h + 1) * d)
+            kr = slice(b * nk, (b + 1) * nk)
+            out[r, c], l, det[r, c], sig[r, c], le = sdpa(q[r, c], k[kr, c], vv[kr, c], scale, bool(p.causal))
+            lse[b * H + h], lerr[b * H + h] = l / LN2, le / LN2 + 2 * U32 * (l / LN2).abs()
+    res = {"out": expect(out, det, F16, sig, CAP["attention"])}
+    if "lse" in v:
+        res["lse"] = Expect(lse, lerr + store_bound(lse, F32), 0.0, F32)
+    return res
+
+
+# ===================================================================================================================== cross attention
+def _fusion(p, v):
+    if "fusion" in v:
+        f = v["fusion"].reshape(-1).double().cpu()
+        return float(f[0]), float(f[1])
+    return float(p.w_text), float(p.w_ip)
+
+
+def xattn_core(q, kt, vt, kip, vip, B, H, nq, nt, nip, d, wt, wi, q_sig=None, q_det=None):
+    """Dual-branch SDPA with two independent softmaxes, one image at a time (heads batched): (out, det, sig), [B*nq, H*d]."""
+    scale = 1.0 / math.sqrt(d)
+    heads = lambda t, n, b: None if t is None else t[b * n:(b + 1) * n].reshape(n, H, d).permute(1, 0, 2)     # [H, n, d]
+    back = lambda t: t.permute(1, 0, 2).reshape(nq, H * d)
+    out = torch.zeros(B * nq, H * d, dtype=torch.float64, device=q.device)
+    det, var = torch.zeros_like(out), torch.zeros_like(out)
+    for b in range(B):
+        r = slice(b * nq, (b + 1) * nq)
+        qh = heads(q, nq, b)
+        for w_, K_, V_, n in ((wt, kt, vt, nt), (wi, kip, vip, nip)):
+            if n == 0 or w_ == 0.0:
+                continue
+            o, _, dt, sg, _ = sdpa(qh, heads(K_, n, b), heads(V_, n, b), scale, q_sig=heads(q_sig, nq, b), q_det=heads(q_det, nq, b))
+            out[r] += w_ * back(o)
+            det[r] += abs(w_) * back(dt)
+            var[r] += (w_ * back(sg)) ** 2
+    return out, det, torch.sqrt(var)
+
+
+def _vnorm(vip, B, H, nip, d):
+    v3 = vip.reshape(B, nip, H, d)
+    n = v3.norm(dim=3).permute(0, 2, 1).reshape(B * H, nip)
+    # fp32 sum of d squares, then sqrt: gamma(d) / 2 + one ulp
+    return n, (gamma(d) + 2 * U32) * n + 2.0 ** -140
+
+
+def layout_xattn(p):
+    C = p.heads * p.d
+    L = {"q": Buf(F16, p.batch * p.nq, C, p.ldq), "kt": Buf(F16, p.batch * p.nt, C, p.ldkt), "vt": Buf(F16, p.batch * p.nt, C, p.ldvt),
+         "out": Buf(F16, p.batch * p.nq, C, p.ldo, "out")}
+    if p.nip:
+        L.update(kip=Buf(F16, p.batch * p.nip, C, p.ldkip), vip=Buf(F16, p.batch * p.nip, C, p.ldvip))
+    if _ptr(p, "vnorm"):
+        L["vnorm"] = Buf(F32, p.batch * p.heads, p.nip, p.nip, "out")
+    if _ptr(p, "fusion"):
+        L["fusion"] = Buf(F32, 1, 2, 2)
+    return L
+
+
+def ref_xattn(p, v):
+    wt, wi = _fusion(p, v)
+    kip = f64(v["kip"]) if "kip" in v else None
+    vip = f64(v["vip"]) if "vip" in v else None
+    out, det, sig = xattn_core(f64(v["q"]), f64(v["kt"]), f64(v["vt"]), kip, vip, p.batch, p.heads, p.nq, p.nt, p.nip, p.d, wt, wi)
+    res = {"out": expect(out, det, F16, sig, CAP["xattn"])}
+    if "vnorm" in v:
+        n, b = _vnorm(vip, p.batch, p.heads, p.nip, p.d)
+        res["vnorm"] = Expect(n, b, 0.0, F32)
+    return res
+
+
+def layout_xattn_lnq(p):
+    C = p.heads * p.d
+    L = {"hs": Buf(F16, p.batch * p.nq, C, p.ld_hs), "wq": Buf(F16, C, C, C), "kt": Buf(F16, p.batch * p.nt, C, p.ldkt),
+         "vt": Buf(F16, p.batch * p.nt, C, p.ldvt), "out": Buf(F16, p.batch * p.nq, C, p.ldo, "out")}
+    if _ptr(p, "q_bias"):
+        L["q_bias"] = Buf(F32, 1, C, C)
+    if _ptr(p, "wq_rowsum"):
+        L["wq_rowsum"] = Buf(F32, 1, C, C)
+    if p.nip:
+        L.update(kip=Buf(F16, p.batch * p.nip, C, p.ldkip), vip=Buf(F16, p.batch * p.nip, C, p.ldvip))
+    if _ptr(p, "vnorm"):
+        L["vnorm"] = Buf(F32, p.batch * p.heads, p.nip, p.nip, "out")
+    if _ptr(p, "fusion"):
+        L["fusion"] = Buf(F32, 1, 2, 2)
+    return L
+
+
+def q_stage(p, v, C, round_x: bool):
+    """q = to_q(LayerNorm_noaffine(hs)) + q_bias (or to_q(hs) + q_bias) and its error terms (det, sig), q's own fp16 rounding included.
+    ``round_x``: the normalised rows are rounded to fp16 before the product (the fused launch's register-resident X)."""
+    x = f64(v["hs"])
+    wq = f64(v["wq"])
+    if p.ln:
+        mean = x.mean(1, keepdim=True)
+        rstd = 1.0 / torch.sqrt(((x - mean) ** 2).mean(1, keepdim=True) + float(p.ln_eps))
+        xn = (x - mean) * rstd
+    else:
+        xn = x
+    q = xn @ wq.T
+    if p.ln and not round_x:
+        # the folded form rstd * (wq . x - mean * rowsum): accumulation over the raw rows, then the cancellation
+        det = rstd * mfma_c(C) * (x.abs() @ wq.abs().T + mean.abs() * wq.abs().sum(1)[None, :])
+    else:
+        det = mfma_c(C) * (xn.abs() @ wq.abs().T)
+    var = torch.zeros_like(q)
+    if p.ln:
+        det = det + 2 * gamma(C) * q.abs()             # fp32 row statistics: relative gamma(C) on mean and variance
+        if round_x:
+            var = var + (U16 * xn) ** 2 @ (wq * wq).T  # X normalised in registers, rounded to fp16 for the MFMA
+    if "q_bias" in v:
+        q = q + f64(v["q_bias"]).reshape(1, -1)
+    var = var + (U16 * q) ** 2 + SUB16 ** 2           # q (pre-scaled) is an fp16 MFMA operand of the score product
+    return q, det, torch.sqrt(var)
+
+
+def ref_xattn_lnq(p, v):
+    C = p.heads * p.d
+    wt, wi = _fusion(p, v)
+    q, qdet, qsig = q_stage(p, v, C, round_x=False)
+    kip = f64(v["kip"]) if "kip" in v else None
+    vip = f64(v["vip"]) if "vip" in v else None
+    out, det, sig = xattn_core(q, f64(v["kt"]), f64(v["vt"]), kip, vip, p.batch, p.heads, p.nq, p.nt, p.nip, p.d, wt, wi, q_sig=qsig, q_det=qdet)
+    res = {"out": expect(out, det, F16, sig, CAP["lnq"])}
+    if "vnorm" in v:
+        n, b = _vnorm(vip, p.batch, p.heads, p.nip, p.d)
+        res["vnorm"] = Expect(n, b, 0.0, F32)
+    return res
+
+
+def layout_xattn_fused(p):
+    C = p.heads * p.d
+    L = {"hs": Buf(F16, p.batch * p.nq, C, p.ld_hs), "wq": Buf(F16, C, C, C), "wo": Buf(F16, C, C, C),
+         "kimg": Buf(F16, 1, p.batch * p.heads * 96 * (64 if p.d == 40 else 128), 0),
+         "vimg": Buf(F16, 1, p.batch * (C // 80) * 96 * 80, 0), "out": Buf(F16, p.batch * p.nq, C, p.ld_out, "out")}
+    if _ptr(p, "q_bias"):
+        L["q_bias"] = Buf(F32, 1, C, C)
+    if _ptr(p, "bias_o"):
+        L["bias_o"] = Buf(F32, 1, C, C)
+    if _ptr(p, "fusion"):
+        L["fusion"] = Buf(F32, 1, 2, 2)
+    return L
+
+
+def ref_xattn_fused(p, v, kv, wo_slot):
+    """``kv``: (kt, vt, kip, vip) - the K / V rows ``pv_xattn_pack_kv`` built ``kimg`` / ``vimg`` from (their layout is not documented);
+    ``wo_slot``: packed column s -> natural column (``pv_xattn_fused_wo_slot``).  Checked twice: the whole output (with its residual) at the
+    kernel test's 1e-3, and the attention part (out - hs) at its 3e-3."""
+    C = p.heads * p.d
+    wt, wi = _fusion(p, v)
+    q, qdet, qsig = q_stage(p, v, C, round_x=True)
+    kt, vt, kip, vip = (None if t is None else f64(t) for t in kv)
+    ctx, cdet, csig = xattn_core(q, kt, vt, kip, vip, p.batch, p.heads, p.nq, p.nt, p.nip, p.d, wt, wi, q_sig=qsig, q_det=qdet)
+    wo_p = f64(v["wo"])
+    wo = torch.empty_like(wo_p)
+    wo[:, torch.as_tensor(wo_slot, device=wo.device)] = wo_p
+    att = ctx @ wo.T
+    # ctx's errors and its fp16 rounding (ctx is the MFMA operand of to_out) through wo, and to_out's accumulation
+    det = cdet @ wo.abs().T + mfma_c(C) * (ctx.abs() @ wo.abs().T)
+    sig = torch.sqrt((csig ** 2 + (U16 * ctx) ** 2 + SUB16 ** 2) @ (wo * wo).T)
+    if "bias_o" in v:
+        att = att + f64(v["bias_o"]).reshape(1, -1)
+    hs = f64(v["hs"])
+    out = att + hs
+    e_out = expect(out, det, F16, sig, CAP["fused"])
+    e_att = expect(att, det, F16, sig, CAP["fused_attn"])
+    e_att.bound = e_out.bound                     # the one fp16 store is of out = hs + att
+    e_att.derive = lambda got, hs=hs: got["out"].double() - hs
+    e_att.rounded = out.to(F16).double() - hs
+    return {"out": e_out, "out - hs": e_att}
+
+
+def ref_pack_kv(a, v):
+    res = {}
+    if "vnorm" in v:
+        n, b = _vnorm(f64(v["vip"]), a.batch, a.heads, a.nip, a.d)
+        res["vnorm"] = Expect(n, b, 0.0, F32)
+    return res
+
+
+def layout_pack_kv(a):
+    C = a.heads * a.d
+    L = {"kt": Buf(F16, a.batch * a.nt, C, a.ldkt), "vt": Buf(F16, a.batch * a.nt, C, a.ldvt),
+         "kimg": Buf(F16, 1, a.batch * a.heads * 96 * (64 if a.d == 40 else 128), 0, "opaque"),
+         "vimg": Buf(F16, 1, a.batch * (C // 80) * 96 * 80, 0, "opaque")}
+    if a.nip:
+        L.update(kip=Buf(F16, a.batch * a.nip, C, a.ldkip), vip=Buf(F16, a.batch * a.nip, C, a.ldvip))
+    if a.vnorm:
+        L["vnorm"] = Buf(F32, a.batch * a.heads, a.nip, a.nip, "out")
+    return L
+
+
+# ===================================================================================================================== row GEMM / norms
+def layout_row_gemm(p):
+    n_out = p.N // 2 if p.geglu else p.N
+    L = {"x": Buf(F16, p.M, p.K, p.ld_x), "w": Buf(F16, p.N, p.K, p.K), "out": Buf(F16, p.M, n_out, p.ld_out, "out")}
+    if _ptr(p, "bias"):
+        L["bias"] = Buf(F32, 1, p.N, p.N)
+    if _ptr(p, "x_norm"):
+        L["x_norm"] = Buf(F32, p.M // p.rows_per_image, 2 * p.K, 2 * p.K)
+    return L
+
+
+def ref_row_gemm(p, v):
+    x = f64(v["x"])
+    w = f64(v["w"])
+    det_in = sig_in = None
+    if p.ln:
+        mean = x.mean(1, keepdim=True)
+        rstd = 1.0 / torch.sqrt(((x - mean) ** 2).mean(1, keepdim=True) + float(p.ln_eps))
+        x = (x - mean) * rstd
+        det_in = 2 * gamma(p.K) * x.abs()                             # fp32 row statistics
+        sig_in = U16 * x.abs() + SUB16                                # rows normalised in registers, rounded to fp16 for the MFMA
+    elif "x_norm" in v:
+        tab = f64(v["x_norm"]).reshape(-1, 2, p.K)
+        img = torch.arange(p.M, device=x.device) // p.rows_per_image
+        x = (x * tab[img, 0] + tab[img, 1]).to(F16).to(torch.float64)   # rounded to fp16 exactly as pv_groupnorm_apply writes it
+        sig_in = U16 * x.abs()                                        # the same fp32 value rounded: a rare one-ulp flip
+    acc = x @ w.T
+    err = mfma_c(p.K) * (x.abs() @ w.abs().T)
+    if det_in is not None:
+        err = err + det_in @ w.abs().T
+    sig = None if sig_in is None else torch.sqrt(sig_in ** 2 @ (w * w).T)
+    if "bias" in v:
+        acc = acc + f64(v["bias"]).reshape(1, -1)
+    if p.geglu:
+        col, gate = rowgemm_unpack_geglu(p.N)
+        col, gate = col.to(acc.device), gate.to(acc.device)
+        n_out = p.N // 2
+        val, gt = torch.empty(p.M, n_out, dtype=torch.float64, device=acc.device), torch.empty(p.M, n_out, dtype=torch.float64, device=acc.device)
+        ev, eg = torch.empty_like(val), torch.empty_like(val)
+        val[:, col[~gate]], gt[:, col[gate]] = acc[:, ~gate], acc[:, gate]
+        ev[:, col[~gate]], eg[:, col[gate]] = err[:, ~gate], err[:, gate]
+        g = _gelu(gt)
+        acc = val * g
+        err = ev * g.abs() + val.abs() * (DACT * eg + GELU_APPROX * gt.abs())
+        if sig is not None:
+            sv, sg = torch.empty_like(val), torch.empty_like(val)
+            sv[:, col[~gate]], sg[:, col[gate]] = sig[:, ~gate], sig[:, gate]
+            sig = torch.sqrt((sv * g) ** 2 + (DACT * val * sg) ** 2)
+    return {"out": expect(acc, err, F16, sig, CAP["row_gemm"])}
+
+
+def layout_layernorm(p):
+    return {"x": Buf(F16, p.rows, p.cols, p.ldx), "y": Buf(F16, p.rows, p.cols, p.ldy, "out"), "gamma": Buf(F32, 1, p.cols, p.cols),
+            "beta": Buf(F32, 1, p.cols, p.cols)}
+
+
+def ref_layernorm(p, v):
+    x = f64(v["x"])
+    mean = x.mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((x - mean) ** 2).mean(1, keepdim=True) + float(p.eps))
+    g = f64(v["gamma"]).reshape(1, -1)
+    z = g * (x - mean) * rstd
+    y = _act(z + f64(v["beta"]).reshape(1, -1), p.act)
+    # fp32 statistics (gamma(cols) relative on mean and variance -> 2 gamma on the normalised value) and the affine ops' roundings
+    err = DACT * ((2 * gamma(p.cols) + 4 * U32) * z.abs() + g.abs() * rstd * gamma(p.cols) * x.abs().mean(1, keepdim=True) + 2 * U32 * y.abs())
+    return {"y": expect(y, err, F16, cap=CAP["layernorm"])}
+
+
+def layout_groupnorm(p, table=False):
+    B, G = p.batch, p.groups
+    Ct = p.c0 + p.c1
+    L = {"x0": Buf(F16, B * p.hw, p.c0, p.ld0)}
+    L["partial"] = Buf(F32, B * p.splits, 2 * G, 2 * G, "scratch")
+    if p.c1:
+        L["x1"] = Buf(F16, B * p.hw, p.c1, p.ld1)
+    return L, B, G, Ct
+
+
+def group_stats(p, v):
+    """(mean, rstd) per (image, group) of x0 | x1 over hw pixels x C/G channels, with their error bounds."""
+    B, G = p.batch, p.groups
+    x = f64(v["x0"]) if p.c1 == 0 else torch.cat([f64(v["x0"]), f64(v["x1"])], 1)
+    C = x.shape[1]
+    xg = x.reshape(B, p.hw, G, C // G).permute(0, 2, 1, 3).reshape(B, G, -1)
+    n = xg.shape[2]
+    mean = xg.mean(2)
+    var = ((xg - mean[..., None]) ** 2).mean(2)
+    ex2 = (xg * xg).mean(2)
+    rstd = 1.0 / torch.sqrt(var + float(p.eps))
+    # fp32 sums of n terms (sum and sum of squares, or the column statistics' 64-row sums + their reduction): gamma(n) relative on each;
+    # var = E[x^2] - mean^2 then carries 2 gamma(n) E[x^2] absolute; rstd = (var + eps)^-1/2 halves the relative error, + its own ulps
+    e_mean = gamma(n) * xg.abs().mean(2) + 2.0 ** -140
+    e_var = 2 * gamma(n) * ex2 + 2 * mean.abs() * e_mean
+    e_rstd = 0.5 * rstd * e_var / (var + float(p.eps)) + 4 * U32 * rstd
+    return mean, rstd, e_mean, e_rstd
+
+
+def layout_gn_stats(p):
+    L, B, G, Ct = layout_groupnorm(p)
+    if _ptr(p, "colstats0"):
+        L["colstats0"] = Buf(F32, (B * p.hw + 63) // 64, 2 * p.c0, 2 * p.c0)
+    if p.c1 and _ptr(p, "colstats1"):
+        L["colstats1"] = Buf(F32, (B * p.hw + 63) // 64, 2 * p.c1, 2 * p.c1)
+    return L
+
+
+def _stats_expect(p, v):
+    mean, rstd, em, er = group_stats(p, v)
+    ref = torch.stack([mean, rstd], 2)          # [B][G][2] at partial[b][0][g][0..1]
+    bound = torch.stack([em + store_bound(mean, F32), er + store_bound(rstd, F32)], 2)
+    return ref, bound
+
+
+def ref_gn_stats(p, v):
+    ref, bound = _stats_expect(p, v)
+    return {"partial[:, 0]": Expect(ref.reshape(p.batch, 2 * p.groups), bound.reshape(p.batch, 2 * p.groups), 0.0, F32)}
+
+
+def layout_gn_scale_shift(p):
+    L = layout_gn_stats(p)
+    L["table"] = Buf(F32, p.batch, 2 * (p.c0 + p.c1), 2 * (p.c0 + p.c1), "out")
+    L["gamma"] = Buf(F32, 1, p.c0 + p.c1, p.c0 + p.c1)
+    L["beta"] = Buf(F32, 1, p.c0 + p.c1, p.c0 + p.c1)
+    return L
+
+
+def ref_gn_scale_shift(p, v):
+    mean, rstd, em, er = group_stats(p, v)
+    Ct = p.c0 + p.c1
+    grp = torch.arange(Ct, device=mean.device) // (Ct // p.groups)
+    g, b = f64(v["gamma"]).reshape(1, -1), f64(v["beta"]).reshape(1, -1)
+    sc = g * rstd[:, grp]
+    sh = b - mean[:, grp] * sc
+    esc = g.abs() * er[:, grp] + 2 * U32 * sc.abs()
+    esh = mean[:, grp].abs() * esc + sc.abs() * em[:, grp] + 2 * U32 * (b.abs() + (mean[:, grp] * sc).abs())
+    ref = torch.stack([sc, sh], 1).reshape(p.batch, 2 * Ct)
+    bound = torch.stack([esc, esh], 1).reshape(p.batch, 2 * Ct) + store_bound(ref, F32)
+    sref, sbound = _stats_expect(p, v)
+    return {"table": Expect(ref, bound, 0.0, F32),
+            "partial[:, 0]": Expect(sref.reshape(p.batch, 2 * p.groups), sbound.reshape(p.batch, 2 * p.groups), 0.0, F32)}
+
+
+def layout_gn_apply(p):
+    L, B, G, Ct = layout_groupnorm(p)
+    L["partial"] = Buf(F32, B * p.splits, 2 * G, 2 * G, "in")
+    L["gamma"] = Buf(F32, 1, Ct, Ct)
+    L["beta"] = Buf(F32, 1, Ct, Ct)
+    L["y"] = Buf(F16, B * p.hw, Ct, Ct, "out")
+    return L
+
+
+def ref_gn_apply(p, v):
+    """y = act(gamma (x - mean) rstd + beta) with the (mean, rstd) the statistics launch left in partial[b][0][g] (an input here)."""
+    B, G = p.batch, p.groups
+    x = f64(v["x0"]) if p.c1 == 0 else torch.cat([f64(v["x0"]), f64(v["x1"])], 1)
+    Ct = x.shape[1]
+    st = f64(v["partial"]).reshape(B, p.splits, G, 2)[:, 0]
+    grp = torch.arange(Ct, device=x.device) // (Ct // G)
+    img = torch.arange(B * p.hw, device=x.device) // p.hw
+    mean, rstd = st[img][:, grp, 0], st[img][:, grp, 1]
+    g, b = f64(v["gamma"]).reshape(1, -1), f64(v["beta"]).reshape(1, -1)
+    z = g * (x - mean) * rstd
+    y = _act(z + b, p.act)
+    err = DACT * 4 * U32 * (z.abs() + g.abs() * (x.abs() + mean.abs()) * rstd + b.abs())
+    return {"y": expect(y, err, F16, cap=CAP["groupnorm"])}
+
+
+# ===================================================================================================================== small launchers
+def layout_im2col(a):
+    return {"x": Buf(F32, 1, a.batch * a.cin * a.h * a.wd, 0), "out": Buf(F16, a.batch * a.h * a.wd, a.kpad, a.kpad, "out")}
+
+
+def ref_im2col(a, v):
+    x = v["x"].reshape(a.batch, a.cin, a.h, a.wd).permute(0, 2, 3, 1).reshape(-1, a.cin)
+    taps = conv_taps(x.double(), a.batch, a.h, a.wd, a.h, a.wd, 1, 0, 1)        # tap t -> [pixels, cin]
+    cols = torch.stack(taps, 2).reshape(-1, a.cin * 9)                         # column k = ci * 9 + t
+    out = torch.zeros(a.batch * a.h * a.wd, a.kpad, dtype=torch.float64, device=x.device)
+    out[:, :a.cin * 9] = cols
+    return {"out": Expect(out.to(F16).double(), torch.zeros_like(out), 0.0, None)}
+
+
+def layout_conv_out(a):
+    return {"x": Buf(F16, a.batch * a.h * a.wd, a.cin, a.cin), "w": Buf(F16, a.cout, 9 * a.cin, 9 * a.cin), "bias": Buf(F32, 1, a.cout, a.cout),
+            "out": Buf(F32, a.batch * a.cout, a.h * a.wd, a.h * a.wd, "out")}
+
+
+def ref_conv_out(a, v):
+    x, w = f64(v["x"]), f64(v["w"])
+    acc = torch.zeros(a.batch * a.h * a.wd, a.cout, dtype=torch.float64, device=x.device)
+    S = torch.zeros_like(acc)
+    for t, xt in enumerate(conv_taps(x, a.batch, a.h, a.wd, a.h, a.wd, 1, 0, 1)):
+        wt = w[:, t * a.cin:(t + 1) * a.cin]
+        acc += xt @ wt.T
+        S += xt.abs() @ wt.abs().T
+    acc = acc + f64(v["bias"]).reshape(1, -1)
+    ref = acc.reshape(a.batch, a.h * a.wd, a.cout).permute(0, 2, 1).reshape(a.batch * a.cout, a.h * a.wd)
+    err = (mfma_c(9 * a.cin) * S).reshape(a.batch, a.h * a.wd, a.cout).permute(0, 2, 1).reshape(a.batch * a.cout, a.h * a.wd)
+    return {"out": expect(ref, err, F32, cap=CAP["conv_out"])}
+
+
+def step_index(state: torch.Tensor) -> int:
+    s = state.reshape(-1).cpu().tolist()
+    return min(s[0], s[1] - 1) if s[1] > 0 else s[0]
+
+
+def layout_timestep(a):
+    L = {"timesteps": Buf(F32, 1, max(a.rows, 1), 0), "out": Buf(F16, a.rows, a.dim, a.dim, "out")}
+    if a.state:
+        L["state"] = Buf(I32, 1, 2, 2)
+        L["timesteps"] = None            # extent known once the state is read (resolved by the audit)
+    return L
+
+
+def ref_timestep(a, v):
+    half = a.dim // 2
+    if "state" in v:
+        t = v["timesteps"].reshape(-1)[step_index(v["state"])].double().reshape(1, 1).expand(a.rows, 1)
+    else:
+        t = f64(v["timesteps"]).reshape(-1)[:a.rows, None]
+    k = torch.arange(half, dtype=torch.float64, device=t.device)
+    arg = t * torch.exp(-math.log(10000.0) * k / half)[None, :]
+    ref = torch.cat([torch.cos(arg), torch.sin(arg)], 1)
+    # fp32: the exponent (9.21 k / half: 2 ulps), expf and the product t * freq (one ulp each) -> 6 U32 |arg| on the argument of cos / sin
+    # (slope <= 1), + cosf / sinf's own 2 ulps
+    extra = 6 * U32 * torch.cat([arg, arg], 1).abs() + 4 * U32
+    return {"out": expect(ref, extra, F16)}
+
+
+def layout_cfg(a):
+    n = a.n
+    return {"eps_uncond": Buf(F32, 1, n, 0), "eps_cond": Buf(F32, 1, n, 0), "latents": Buf(F32, 1, n, 0, "inout"),
+            "x0_prev": Buf(F32, 1, n, 0, "inout"), "coef": None, "state": Buf(I32, 1, 2, 2)}
+
+
+def ref_cfg(a, v):
+    """coef row (8 floats) {ca, cb, cx, c0, c1, -}: e = u + g (c - u); x0 = ca x + cb e; x' = cx x + c0 x0 + c1 x0_prev.  fp32: each of
+    the <= 4 chained roundings is within U32 of the running magnitude sum -> 4 U32 M (x0), and x' also carries c0 x that error: 8 U32 M."""
+    c = v["coef"].reshape(-1).double().cpu().tolist()
+    ca, cb, cx, c0, c1 = c[:5]
+    g = float(a.guidance)
+    u, cc, x, xp = (f64(v[k]) for k in ("eps_uncond", "eps_cond", "latents", "x0_prev"))
+    e = u + g * (cc - u)
+    x0 = ca * x + cb * e
+    xn = cx * x + c0 * x0 + c1 * xp
+    me = u.abs() + abs(g) * (cc.abs() + u.abs())
+    mx0 = abs(ca) * x.abs() + abs(cb) * me
+    mx = abs(cx) * x.abs() + abs(c0) * mx0 + abs(c1) * xp.abs()
+    return {"latents": Expect(xn, 8 * U32 * mx + 2.0 ** -140, 0.0, F32), "x0_prev": Expect(x0, 4 * U32 * mx0 + 2.0 ** -140, 0.0, F32)}
+
+
+def layout_step_advance(a):
+    return {"state": Buf(I32, 1, 1, 1, "inout")}
+
+
+def ref_step_advance(a, v):
+    s = v["state"].reshape(-1).double()
+    return {"state": Expect((s + 1).reshape(1, 1), torch.zeros(1, 1, dtype=torch.float64, device=s.device), 0.0, None)}
+
+
+def layout_pointwise(a):
+    return {"x": Buf(F32, a.batch * a.cin, a.hw, a.hw), "w": Buf(F32, a.cout, a.cin, a.cin), "bias": Buf(F32, 1, a.cout, a.cout),
+            "out": Buf(F32, a.batch * a.cout, a.hw, a.hw, "out")}
+
+
+def ref_pointwise(a, v):
+    x = f64(v["x"]).reshape(a.batch, a.cin, a.hw)
+    w = f64(v["w"])
+    out = torch.einsum("oc,bcp->bop", w, x)
+    S = torch.einsum("oc,bcp->bop", w.abs(), x.abs())
+    if "bias" in v:
+        b = f64(v["bias"]).reshape(1, -1, 1)
+        out, S = out + b, S + b.abs()
+    # a (cin + 1)-term fp32 fma chain
+    return {"out": expect(out.reshape(a.batch * a.cout, a.hw), gamma(a.cin + 1) * S.reshape(a.batch * a.cout, a.hw), F32)}
+
+
+def layout_softmax_rows(a):
+    return {"x": Buf(F16, a.rows, a.cols, a.ld, "inout")}
+
+
+def ref_softmax_rows(a, v):
+    s = f64(v["x"]) * float(a.scale)
+    p = torch.softmax(s, 1)
+    # exp2 of an fp32 fma argument (one ulp of |s log2 e| + |max| -> ln2 x that relative) and exp2's own ulp, the cols-term normaliser,
+    # the reciprocal and the product: each relative to p
+    arg = (s.abs() + s.max(1, keepdim=True).values.abs()) / LN2
+    rel = LN2 * 2 * U32 * arg + gamma(a.cols) + 6 * U32
+    return {"x": expect(p, rel * p, F16)}
+
+
+def layout_posterior(a):
+    n = a.batch * a.chw
+    return {"moments": Buf(F32, a.batch, 2 * a.chw, 2 * a.chw), "eps": Buf(F32, 1, n, 0), "out": Buf(F32, 1, n, 0, "out")}
+
+
+def ref_posterior(a, v):
+    m = f64(v["moments"]).reshape(a.batch, 2, a.chw)
+    mean, logvar = m[:, 0], m[:, 1].clamp(-30.0, 20.0)
+    sd = torch.exp(0.5 * logvar)
+    e = f64(v["eps"]).reshape(a.batch, a.chw)
+    out = mean + sd * e
+    # __expf = exp2(x log2 e): the product's ulp times |x| (relative on exp), exp2's ulp, then the fma
+    term = (sd * e).abs() * (2 * U32 * (0.5 * logvar).abs() / LN2 * LN2 + 4 * U32) + 2 * U32 * (mean.abs() + (sd * e).abs())
+    return {"out": expect(out.reshape(1, -1), term.reshape(1, -1), F32)}
+
+
+# ===================================================================================================================== tables
+#: positional argument names of the launchers that take no parameter struct (``_lib.SIGNATURES`` order, stream excluded)
+ARGS = {
+    "pv_xattn_pack_kv": ("kt", "vt", "ldkt", "ldvt", "kip", "vip", "ldkip", "ldvip", "kimg", "vimg", "vnorm", "batch", "heads", "d", "nt", "nip"),
+    "pv_im2col3x3": ("x", "out", "batch", "cin", "h", "wd", "kpad"),
+    "pv_conv_out": ("x", "w", "bias", "out", "batch", "cin", "h", "wd", "cout"),
+    "pv_timestep_embedding": ("timesteps", "state", "rows", "dim", "out"),
+    "pv_cfg_dpm_step": ("eps_uncond", "eps_cond", "latents", "x0_prev", "coef", "state", "guidance", "n"),
+    "pv_step_advance": ("state",),
+    "pv_pointwise_nchw": ("x", "w", "bias", "out", "batch", "cin", "cout", "hw"),
+    "pv_softmax_rows": ("x", "ld", "rows", "cols", "scale"),
+    "pv_posterior_sample": ("moments", "eps", "out", "batch", "chw"),
+    "pv_groupnorm_scale_shift": ("table",),       # after the struct
+}
+
+LAYOUT = {
+    "pv_gemm_conv": layout_gemm, "pv_attention": layout_attention, "pv_cross_attention": layout_xattn,
+    "pv_cross_attention_lnq": layout_xattn_lnq, "pv_cross_attention_fused": layout_xattn_fused, "pv_xattn_pack_kv": layout_pack_kv,
+    "pv_row_gemm": layout_row_gemm, "pv_layernorm": layout_layernorm, "pv_groupnorm_stats": layout_gn_stats,
+    "pv_groupnorm_stats_from_colstats": layout_gn_stats, "pv_groupnorm_scale_shift": layout_gn_scale_shift, "pv_groupnorm_apply": layout_gn_apply,
+    "pv_im2col3x3": layout_im2col, "pv_conv_out": layout_conv_out, "pv_timestep_embedding": layout_timestep, "pv_cfg_dpm_step": layout_cfg,
+    "pv_step_advance": layout_step_advance, "pv_pointwise_nchw": layout_pointwise, "pv_softmax_rows": layout_softmax_rows,
+    "pv_posterior_sample": layout_posterior,
+}
+
+REF = {
+    "pv_gemm_conv": ref_gemm, "pv_attention": ref_attention, "pv_cross_attention": ref_xattn, "pv_cross_attention_lnq": ref_xattn_lnq,
+    "pv_cross_attention_fused": ref_xattn_fused, "pv_xattn_pack_kv": ref_pack_kv, "pv_row_gemm": ref_row_gemm, "pv_layernorm": ref_layernorm,
+    "pv_groupnorm_stats": ref_gn_stats, "pv_groupnorm_stats_from_colstats": ref_gn_stats, "pv_groupnorm_scale_shift": ref_gn_scale_shift,
+    "pv_groupnorm_apply": ref_gn_apply, "pv_im2col3x3": ref_im2col, "pv_conv_out": ref_conv_out, "pv_timestep_embedding": ref_timestep,
+    "pv_cfg_dpm_step": ref_cfg, "pv_step_advance": ref_step_advance, "pv_pointwise_nchw": ref_pointwise, "pv_softmax_rows": ref_softmax_rows,
+    "pv_posterior_sample": ref_posterior,
+}
+
+#: struct fields no layout / reference reads, and why.  Every other field of an audited struct is read by its layout or its reference
+#: (``fields_read``); a field in neither fails ``test_abi_ref_cpu.py``'s coverage test until it is modelled or listed here.
+DISPATCH_ONLY = {
+    "GemmParams": {"big_tile_min": "dispatch: the minimum tile count of the 256-row-tile kernel; every kernel computes the same product",
+                   "splitk_ws": "scratch: the fp32 partial slabs of a split-K launch, reduced in fixed order"},
+    "XAttnFusedParams": {"rows_per_workgroup": "dispatch: 64- or 128-row workgroups, the same results (ABI 13)"},
+}
+
+#: per ctypes struct (``photoverse_amd._lib``): the functions of this module that read its fields
+STRUCT_FUNCS = {
+    "GemmParams": (layout_gemm, ref_gemm, gemm_geometry),
+    "AttnParams": (layout_attention, ref_attention),
+    "XAttnParams": (layout_xattn, ref_xattn, _fusion),
+    "XAttnLnqParams": (layout_xattn_lnq, ref_xattn_lnq, q_stage, _fusion),
+    "XAttnFusedParams": (layout_xattn_fused, ref_xattn_fused, q_stage, _fusion),
+    "RowGemmParams": (layout_row_gemm, ref_row_gemm),
+    "LayerNormParams": (layout_layernorm, ref_layernorm),
+    "GroupNormParams": (layout_groupnorm, layout_gn_stats, layout_gn_scale_shift, layout_gn_apply, group_stats, ref_gn_stats, ref_gn_scale_shift,
+                        ref_gn_apply),
+}
+
+
+def fields_read(struct: str) -> set:
+    """Fields of ``struct`` its layout / reference functions mention: ``p.<field>``, a buffer key ``"<field>": Buf(`` / ``L["<field>"]`` /
+    ``<field>=Buf(``, ``v["<field>"]`` or ``"<field>" in v`` - lines that declare a scratch buffer do not count.  A tripwire for fields added
+    to the ABI, not a proof that a field's meaning is modelled: that is what the CPU tests against independent formulations check."""
+    import inspect
+    import re
+    names = set()
+    for fn in STRUCT_FUNCS[struct]:
+        for line in inspect.getsource(fn).splitlines():
+            if '"scratch"' in line:
+                continue
+            names |= set(re.findall(r"\bp\.(\w+)", line)) | set(re.findall(r'"(\w+)": Buf\(', line)) | set(re.findall(r'L\["(\w+)"\]', line))
+            names |= set(re.findall(r"(\w+)=Buf\(", line)) | set(re.findall(r'"(\w+)" in v', line)) | set(re.findall(r'v\["(\w+)"\]', line))
+    return names

@@ -256,7 +256,7 @@ class Recorder:
         p = GemmParams(_ptr(a), _ptr(a1), c0, c1, lda0, lda1, _ptr(w), _ptr(bias), _ptr(rowadd), rowadd_ld, _ptr(residual), ldr,
                        _ptr(out), ldc, M, N, taps, *geo, act, int(out_f32), int(geglu), splitk, _ptr(ws), _ptr(cs), _ptr(ln_rowsum), float(ln_eps), big_min if big_min > 0 else -1,
                        _ptr(a_norm), int(a_norm_act))
-        self.keep.extend(t for t in (a, a1, w, bias, rowadd, residual, out, ln_rowsum, a_norm) if t is not None)
+        self.keep.extend(t for t in (a, a1, w, bias, rowadd, residual, out, ln_rowsum, a_norm, cs) if t is not None)   # cs: a caller-owned colstats_out too
         # the symbol rocprofv3 shows for this launch and its workgroup count (4th tag field: bench.py separates the chip-filling launches of the
         # one-per-CU tile from the half-chip ones): asked from the library's own dispatch code, not restated here
         try:
@@ -324,7 +324,7 @@ class Recorder:
         table = self.empty((batch, 2, c0 + c1), torch.float32)
         p = GroupNormParams(_ptr(x), _ptr(x1), c0, c1, ld0, ld1, batch, hw, groups, 1, _ptr(partial), _ptr(gamma), _ptr(beta),
                             float(eps), ACT_NONE, None, _ptr(cs0), _ptr(cs1))
-        self.keep.extend(t for t in (x, x1, gamma, beta) if t is not None)
+        self.keep.extend(t for t in (x, x1, gamma, beta, cs0, cs1) if t is not None)   # statistics another plan wrote (DenoiseLoop's merge seam)
         self._add(self.lib.pv_groupnorm_scale_shift, p, _ptr(table))
         return table
 
@@ -353,7 +353,7 @@ class Recorder:
         from_cs = hw % 64 == 0 and cs0 is not None and (x1 is None or cs1 is not None)
         p = GroupNormParams(_ptr(x), _ptr(x1), c0, c1, ld0, ld1, batch, hw, groups, splits, _ptr(partial), _ptr(gamma), _ptr(beta),
                             float(eps), act, _ptr(y), _ptr(cs0) if from_cs else None, _ptr(cs1) if from_cs else None)
-        self.keep.extend(t for t in (x, x1, gamma, beta) if t is not None)
+        self.keep.extend(t for t in (x, x1, gamma, beta) + ((cs0, cs1) if from_cs else ()) if t is not None)
         self._add(self.lib.pv_groupnorm_stats_from_colstats if from_cs else self.lib.pv_groupnorm_stats, p)
         self._add(self.lib.pv_groupnorm_apply, p)
         return (y, partial.view(batch, -1)) if return_stats else y

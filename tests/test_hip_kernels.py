@@ -28,6 +28,31 @@ def h16(*shape, scale=1.0, seed=0):
     return (torch.randn(*shape, generator=g) * scale).half()
 
 
+def test_recorder_holds_a_caller_owned_statistics_buffer(rec_cls):
+    """A launch recorded with ``colstats_out`` writes a buffer the caller owns.  Before, the recorder's only reference to it was its
+    ``colstats`` table entry, and recording the same output again without statistics drops that entry: a caller that then let the buffer go left
+    the first launch writing freed memory.  The recorder now holds every buffer it records by address (in the shipped plans the loop also holds
+    it), so the buffer outlives the caller's reference."""
+    import gc
+    import weakref
+    rec = rec_cls("cuda")
+    a, w = h16(128, 64, seed=1).cuda(), h16(128, 64, scale=0.1, seed=2).cuda()
+    y = torch.empty(128, 128, dtype=torch.float16, device="cuda")
+    cs = torch.zeros(2, 2, 128, dtype=torch.float32, device="cuda")
+    rec.gemm(a, w, out=y, colstats=True, colstats_out=cs)
+    rec.gemm(a, w, out=y)                          # the same output again, without statistics: the table entry goes
+    assert (y.data_ptr(), 128, 128) not in rec.colstats
+    ref = weakref.ref(cs)
+    del cs
+    gc.collect()
+    held = ref()
+    assert held is not None, "the recorded statistics buffer was freed while the plan still writes it"
+    rec.run()
+    torch.cuda.synchronize()
+    yy = y.double().cpu().reshape(2, 64, 128)
+    assert torch.allclose(held.double().cpu()[:, 0], yy.sum(1), rtol=1e-5, atol=1e-4)
+
+
 # small, ragged (M tail) and large-M shapes; K from one K-step to 64 of them
 @pytest.mark.parametrize("M,N,K", [(256, 320, 320), (1000, 640, 768), (16, 1280, 1280), (130, 128, 64), (128, 1024, 4096),
                                    (16384, 640, 640), (32700, 320, 64), (8192, 1024, 128),
