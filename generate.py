@@ -4,6 +4,9 @@
 Same flags and the same call into ``run_inference`` as the reference (``generate.py:21-34,82-85``); additions forced by
 the offline environment: ``--model_path random`` (seeded random-init weights), ``--synthetic_input`` (no image / tokenizer
 files needed), ``--seed``, ``--latent_size``.  Images are written as PNG like the reference (``generate.py:86-90``).
+
+Beyond the reference: ``--mask_image_path`` (inpainting: white = regenerate) with ``--target_image_path`` (the photograph to edit; the identity
+still comes from ``--input_image_path``), ``--strength`` (img2img: run only the last part of the schedule) and ``--no_paste_back``.
 """
 import argparse
 import os
@@ -32,6 +35,12 @@ parser.add_argument("--seed", type=int, default=None)
 parser.add_argument("--latent_size", type=int, default=64)
 parser.add_argument("--image_encoder_path", type=str, default=None,
                     help="Local directory of openai/clip-vit-large-patch14 (default: <model_path>/image_encoder)")
+parser.add_argument("--mask_image_path", type=str, default=None,
+                    help="Greyscale mask, white = regenerate (nearest-neighbour resize to the working resolution): inpaint the target image (needs a VAE)")
+parser.add_argument("--target_image_path", type=str, default=None, help="The photograph to edit (default: the input image)")
+parser.add_argument("--strength", type=float, default=1.0,
+                    help="Fraction of the schedule to run, starting from the noised image (with --from_noised_image or --mask_image_path)")
+parser.add_argument("--no_paste_back", action="store_true", help="Return the decoded image as it is instead of the target's own pixels outside the mask")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -60,7 +69,21 @@ def prepare_example(args, tokenizer):
         # bicubic + centre crop, [-1, 1]); size = 8 * latent (512 for the reference's fixed latent_size 64)
         example["pixel_values_clip"] = clip_image_processor(raw_image)[None].repeat(n, 1, 1, 1)
         example["pixel_values"] = preprocess_image(raw_image, size=8 * args.latent_size, interpolation="bicubic")[None].repeat(n, 1, 1, 1)
+    if getattr(args, "target_image_path", None) is not None:       # the photograph to edit; pixel_values_clip stays the identity image
+        from PIL import Image
+        from photoverse_amd.image_utils import preprocess_image
+        example["pixel_values"] = preprocess_image(Image.open(args.target_image_path), size=8 * args.latent_size,
+                                                   interpolation="bicubic")[None].repeat(n, 1, 1, 1)
     return example
+
+
+def prepare_mask(args):
+    """``--mask_image_path`` -> (1, 1, H, W) in {0, 1} at the resolution of ``pixel_values`` (shared by all samples), or None."""
+    if getattr(args, "mask_image_path", None) is None:
+        return None
+    from PIL import Image
+    from photoverse_amd.image_utils import preprocess_mask
+    return preprocess_mask(Image.open(args.mask_image_path), size=8 * args.latent_size)[None]
 
 
 if __name__ == "__main__":
@@ -86,7 +109,8 @@ if __name__ == "__main__":
     with torch.no_grad():
         out = run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler, device,
                             args.encoder_layers_idx, latent_size=args.latent_size, guidance_scale=args.guidance_scale,
-                            timesteps=args.num_timesteps, from_noised_image=args.from_noised_image, seed=args.seed)
+                            timesteps=args.num_timesteps, from_noised_image=args.from_noised_image, seed=args.seed,
+                            strength=args.strength, inpaint_mask=prepare_mask(args), paste_back=not args.no_paste_back)
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PV_ABI_VERSION 17
+#define PV_ABI_VERSION 18
 
 enum pv_act { PV_ACT_NONE = 0, PV_ACT_SILU = 1, PV_ACT_QUICK_GELU = 2, PV_ACT_LEAKY_RELU = 3, PV_ACT_GELU = 4 };
 
@@ -467,6 +467,16 @@ int pv_conv_out(const void* x, const void* w, const float* bias, float* out, int
 int pv_cfg_dpm_step(const float* eps_uncond, const float* eps_cond, float* latents, float* x0_prev,
                     const float* coef, const int32_t* state, float guidance, int64_t n, void* stream);
 int pv_step_advance(int32_t* state, void* stream);
+/* (ABI 18) pv_cfg_dpm_step + the inpainting blend of a 4-channel UNet, in the same launch.  Nothing in the reference: replaces the
+ * per-step `latents = (1 - init_mask) * init_latents_proper + init_mask * latents` of [EXT] diffusers'
+ * StableDiffusionInpaintPipeline (with init_latents_proper = scheduler.add_noise(image_latents, noise, t_next), the clean
+ * image latents after the last step).  Same contract as pv_cfg_dpm_step; in addition the row's coef[5], coef[6] = {q0, q1}:
+ *   k = q0*known + q1*noise;   latents = m*x_next + (1-m)*k      (m == 1 -> pv_cfg_dpm_step's bits, m == 0 -> k exactly)
+ * mask fp32 [B][1][hw] broadcast over `channels`; known / noise fp32 like latents, read only; x0_prev receives the unblended x0.
+ * hw % 4 == 0 and n % (channels*hw) == 0. */
+int pv_cfg_dpm_step_masked(const float* eps_uncond, const float* eps_cond, float* latents, float* x0_prev,
+                           const float* coef, const int32_t* state, float guidance, const float* mask, const float* known,
+                           const float* noise, int32_t channels, int32_t hw, int64_t n, void* stream);
 
 /* Grad-mode branch fusion of PhotoVerseAttnProcessor2_0 (attention_processor.py:413-420) WITHOUT the reference's per-layer
  * host sync (`torch.rand(1).item()`): one tiny launch draws u ~ U(0,1) per cross-attention layer on the device
@@ -502,6 +512,11 @@ int pv_pointwise_nchw(const float* x, const float* w, const float* bias, float* 
                       int32_t hw, void* stream);
 /* in place clamp of fp32 values (images.clamp(-1, 1), infer.py:122) */
 int pv_clamp_f32(float* x, float lo, float hi, int64_t n, void* stream);
+/* (ABI 18) out = clamp(m*gen + (1-m)*orig, lo, hi) on fp32 NCHW images, mask fp32 [B][1][hw] at pixel resolution, broadcast over
+ * `channels`; out may alias gen; hw % 4 == 0.  Nothing in the reference: replaces the paste-back of an inpainting result onto
+ * the input photograph ([EXT] diffusers apply_overlay) AND the images.clamp(-1, 1) of infer.py:122, in one launch. */
+int pv_composite_clamp_f32(const float* gen, const float* orig, const float* mask, float* out, float lo, float hi, int32_t batch,
+                           int32_t channels, int32_t hw, void* stream);
 /* out[b][i] = ca[b]*x[b][i] (+ cb[b]*y[b][i]): scheduler.add_noise (infer.py:65, train.py:484: ca = sqrt(acp[t_b]),
  * cb = sqrt(1 - acp[t_b])) and the 1/scaling_factor latent scaling (infer.py:121) */
 int pv_affine_rows_f32(const float* x, const float* y, const float* ca, const float* cb, float* out, int64_t per_sample,

@@ -151,6 +151,8 @@ SIGNATURES = {
     "pv_timestep_embedding": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "pv_conv_out": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "pv_cfg_dpm_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
+    "pv_cfg_dpm_step_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_int64, c_void_p]),
     "pv_step_advance": (c_int, [c_void_p, c_void_p]),
     "pv_fusion_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p]),
     "pv_cast_f32_to_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
@@ -162,6 +164,7 @@ SIGNATURES = {
     "pv_posterior_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "pv_reduce_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "pv_clamp_f32": (c_int, [c_void_p, c_float, c_float, c_int64, c_void_p]),
+    "pv_composite_clamp_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_void_p]),
     "pv_im2col3x3": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "pv_patchify": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "pv_clip_vision_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -181,7 +184,7 @@ def kernel_info(fn, params):
         raise ValueError(f"{fn.__name__ if hasattr(fn, '__name__') else 'kernel_info'}: the library rejects this parameter block (hipError {rc})")
     return buf.value.decode(), int(wgs.value)
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 _lib = None
 
 
@@ -205,11 +208,11 @@ def load():
         lib = C.CDLL(LIB)
     except OSError as e:  # pragma: no cover
         raise HipExtensionMissing(f"cannot load {LIB}: {e}") from e
+    if lib.pv_abi_version() != ABI_VERSION:      # before the symbols are bound: a stale .so is told apart by its version, not by a missing symbol
+        raise HipExtensionMissing(f"{LIB} has ABI {lib.pv_abi_version()}, expected {ABI_VERSION}: rebuild it")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args
-    if lib.pv_abi_version() != ABI_VERSION:
-        raise HipExtensionMissing(f"{LIB} has ABI {lib.pv_abi_version()}, expected {ABI_VERSION}: rebuild it")
     _lib = lib
     return lib

@@ -167,6 +167,64 @@ __global__ void cfg_dpm_step_kernel(const float* eu, const float* ec, float* lat
     *reinterpret_cast<float4_t*>(x0p + i) = x0;
 }
 
+// a*x + b*y with each product and the sum rounded on its own: what fp32 host arithmetic computes (hipcc contracts a*x + b*y into a multiply-add otherwise)
+__device__ __forceinline__ float pv_axpby_unfused(float a, float x, float b, float y) {
+#pragma clang fp contract(off)
+    return a * x + b * y;
+}
+
+// cfg_dpm_step_kernel + the 4-channel inpainting blend of the step's result with the known latents noised to the NEXT timestep:
+// coef row {ca, cb, cx, c0, c1, q0, q1, -}
+//   xn = cx*x + c0*x0 + c1*x0_prev               the step above, same expressions (m == 1 reproduces its bits)
+//   k  = q0*known + q1*noise                     add_noise(known, noise, t_next); (q0, q1) = (1, 0) on the last row
+//   x' = m*xn + (1-m)*k                          two products: m == 1 -> xn, m == 0 -> k, exactly
+// k is rounded product by product (pv_axpby_unfused) so that fp32 host arithmetic reproduces the kept region bit for bit.
+// mask [B][1][hw] is broadcast over the channels; hw % 4 == 0, so the four elements of a thread share one plane.  x0_prev gets the unblended x0.
+__global__ void cfg_dpm_step_masked_kernel(const float* eu, const float* ec, float* lat, float* x0p, const float* coef, const int32_t* state,
+                                           float g, const float* __restrict__ mask, const float* __restrict__ known,
+                                           const float* __restrict__ noise, long chw, int hw, long n) {
+    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float* c = coef + (long)pv_step_index(state) * 8;
+    const float ca = c[0], cb = c[1], cx = c[2], c0 = c[3], c1 = c[4], q0 = c[5], q1 = c[6];
+    const long b = i / chw;
+    const int px = (int)((i - b * chw) % hw);
+    const float4_t u = *reinterpret_cast<const float4_t*>(eu + i);
+    const float4_t cc = *reinterpret_cast<const float4_t*>(ec + i);
+    const float4_t m = *reinterpret_cast<const float4_t*>(mask + b * hw + px);
+    const float4_t kn = *reinterpret_cast<const float4_t*>(known + i);
+    const float4_t nz = *reinterpret_cast<const float4_t*>(noise + i);
+    float4_t x = *reinterpret_cast<const float4_t*>(lat + i);
+    float4_t xp = *reinterpret_cast<const float4_t*>(x0p + i);
+    float4_t x0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float e = u[j] + g * (cc[j] - u[j]);
+        x0[j] = ca * x[j] + cb * e;
+        const float xn = cx * x[j] + c0 * x0[j] + c1 * xp[j];
+        const float k = pv_axpby_unfused(q0, kn[j], q1, nz[j]);
+        x[j] = m[j] * xn + (1.f - m[j]) * k;
+    }
+    *reinterpret_cast<float4_t*>(lat + i) = x;
+    *reinterpret_cast<float4_t*>(x0p + i) = x0;
+}
+
+// out = clamp(m*gen + (1-m)*orig, lo, hi) over NCHW fp32 images, mask [B][1][hw] broadcast over the channels (hw % 4 == 0); out may be gen
+__global__ void composite_clamp_kernel(const float* gen, const float* __restrict__ orig, const float* __restrict__ mask, float* out, float lo, float hi,
+                                       long chw, int hw, long n) {
+    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    const long b = i / chw;
+    const int px = (int)((i - b * chw) % hw);
+    const float4_t gv = *reinterpret_cast<const float4_t*>(gen + i);
+    const float4_t ov = *reinterpret_cast<const float4_t*>(orig + i);
+    const float4_t m = *reinterpret_cast<const float4_t*>(mask + b * hw + px);
+    float4_t o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = fminf(fmaxf(m[j] * gv[j] + (1.f - m[j]) * ov[j], lo), hi);
+    *reinterpret_cast<float4_t*>(out + i) = o;
+}
+
 __global__ void step_advance_kernel(int32_t* state) { state[0] += 1; }
 
 // Philox4x32-10 (Salmon et al. 2011): counter-based, so one launch = one independent draw per layer with no stored stream
@@ -539,6 +597,25 @@ extern "C" int pv_cfg_dpm_step(const float* eps_uncond, const float* eps_cond, f
     if (n <= 0 || (n % 4) || !eps_uncond || !eps_cond || !latents || !x0_prev || !coef || !state) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(cfg_dpm_step_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps_uncond,
                        eps_cond, latents, x0_prev, coef, state, guidance, (long)n);
+    return PV_CHECK_LAUNCH();
+}
+
+extern "C" int pv_cfg_dpm_step_masked(const float* eps_uncond, const float* eps_cond, float* latents, float* x0_prev, const float* coef,
+                                      const int32_t* state, float guidance, const float* mask, const float* known, const float* noise,
+                                      int32_t channels, int32_t hw, int64_t n, void* stream) {
+    if (!eps_uncond || !eps_cond || !latents || !x0_prev || !coef || !state || !mask || !known || !noise) return (int)hipErrorInvalidValue;
+    if (channels <= 0 || hw <= 0 || (hw % 4) || n <= 0 || (n % ((int64_t)channels * hw))) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(cfg_dpm_step_masked_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps_uncond,
+                       eps_cond, latents, x0_prev, coef, state, guidance, mask, known, noise, (long)channels * hw, hw, (long)n);
+    return PV_CHECK_LAUNCH();
+}
+
+extern "C" int pv_composite_clamp_f32(const float* gen, const float* orig, const float* mask, float* out, float lo, float hi, int32_t batch,
+                                      int32_t channels, int32_t hw, void* stream) {
+    if (!gen || !orig || !mask || !out || batch <= 0 || channels <= 0 || hw <= 0 || (hw % 4)) return (int)hipErrorInvalidValue;
+    const long chw = (long)channels * hw, n = chw * batch;
+    hipLaunchKernelGGL(composite_clamp_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gen, orig, mask, out, lo, hi,
+                       chw, hw, n);
     return PV_CHECK_LAUNCH();
 }
 

@@ -7,6 +7,7 @@
 * ``preprocess_image`` - ``/root/reference/datasets/utils.py:139-157`` ([EXT] torchvision ``Resize(size)`` +
   ``CenterCrop(size)`` + ``ToTensor`` + ``Normalize(0.5, 0.5)``): short side to ``size`` with the chosen interpolation
   (long side = int(size * long / short)), centre crop (top = round((h - size) / 2)), [-1, 1].
+* ``preprocess_mask`` - beyond the reference: an inpainting mask through ``preprocess_image``'s geometry with nearest-neighbour resampling.
 * ``denormalize`` / ``to_pil`` - ``/root/reference/utils/image_utils.py:6-29``.
 
 Host-side PIL / numpy work on single images (load time, not the hot path).
@@ -60,6 +61,18 @@ def preprocess_image(raw_image, size: int = 512, interpolation: str = "bicubic")
     img = img.crop((left, top, left + size, top + size))
     arr = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255)
     return (arr - 0.5) / 0.5
+
+
+def preprocess_mask(raw_mask, size: int = 512) -> torch.Tensor:
+    """PIL image -> (1, size, size) float32 in {0, 1}: greyscale, white (>= 128) = regenerate.  Same geometry as ``preprocess_image`` (short side
+    to ``size``, centre crop) so that the mask stays aligned with the photograph it was drawn on; nearest neighbour, so it stays binary."""
+    img = raw_mask if raw_mask.mode == "L" else raw_mask.convert("L")
+    img = _resize_short_side(img, size, _pil_resample("nearest"))
+    w, h = img.size
+    top, left = int(round((h - size) / 2.0)), int(round((w - size) / 2.0))
+    img = img.crop((left, top, left + size, top + size))
+    arr = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy())
+    return (arr >= 128).float()[None]
 
 
 def denormalize(image: torch.Tensor) -> torch.Tensor:

@@ -6,6 +6,10 @@ denoising loop (``:98-119``) is the graph-captured ``DenoiseLoop``; the VAE deco
 function returns the final LATENTS (the value of ``latents`` after ``:119``).  ``from_noised_image`` (``:62-65``) starts from
 ``add_noise(vae.encode(pixel_values).latent_dist.sample() * scaling_factor, noise, t_0)``; the posterior sample is drawn on the
 device generator (``torch.manual_seed(seed)`` seeds it like the reference's, the streams of two platforms never match bit for bit).
+
+Beyond the reference ([EXT] diffusers' img2img ``strength`` and inpainting with a 4-channel UNet): ``strength`` starts the loop part-way down
+the schedule from the image noised to that step, ``inpaint_mask`` regenerates only the masked region - the blend with the re-noised known
+latents is part of the solver-step launch (``pv_cfg_dpm_step_masked``) - and ``paste_back`` composites the decoded result onto the input pixels.
 """
 from __future__ import annotations
 
@@ -21,13 +25,37 @@ from .scheduler import DPMSolverMultistepScheduler
 MAX_CACHED_LOOPS = 2
 
 
-def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0) -> DenoiseLoop:
+def strength_start(timesteps: int, strength: float) -> int:
+    """Row of the schedule an img2img run of ``strength`` begins at ([EXT] diffusers ``get_timesteps``): the last ``int(timesteps * strength)`` steps run."""
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength must be in (0, 1], got {strength}")
+    n_run = min(int(timesteps * strength), timesteps)
+    if n_run < 1:
+        raise ValueError(f"strength {strength} leaves no step of {timesteps} to run")
+    return timesteps - n_run
+
+
+def latent_mask(inpaint_mask: torch.Tensor, batch: int, latent_size: int):
+    """``inpaint_mask`` (B or 1, 1, H, W) in [0, 1], 1 = regenerate -> (pixel mask (B, 1, H, W), latent mask (B, 1, S, S)), both fp32 in {0, 1}: binarised
+    at 0.5; a latent cell is regenerated when ANY pixel of its H / S x W / S block is (a max-pool), so no masked pixel is decoded from kept latents."""
+    m = inpaint_mask
+    if m.dim() != 4 or m.shape[1] != 1 or m.shape[0] not in (1, batch):
+        raise ValueError(f"inpaint_mask has shape {tuple(m.shape)}, expected ({batch} or 1, 1, H, W)")
+    H, W = m.shape[2:]
+    if H % latent_size or W % latent_size or H < latent_size or W < latent_size:
+        raise ValueError(f"inpaint_mask is {H} x {W}: not a multiple of latent_size {latent_size}")
+    pix = (m.detach().float().cpu() >= 0.5).float().expand(batch, 1, H, W).contiguous()
+    lat = pix.reshape(batch, 1, latent_size, H // latent_size, latent_size, W // latent_size).amax(dim=(3, 5))
+    return pix, lat
+
+
+def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False) -> DenoiseLoop:
     cache = unet.__dict__.setdefault("_denoise_loops", OrderedDict())
-    key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed))
+    key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed), bool(inpaint))
     loop = cache.pop(key, None)
     if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0):
         loop = DenoiseLoop(unet, batch, latent_size, n_ip, steps, guidance, scheduler=scheduler, training_mode=training_mode,
-                           fusion_seed=fusion_seed)
+                           fusion_seed=fusion_seed, inpaint=inpaint)
         loop.unet_version = unet.__dict__.get("_pack_version", 0)
     cache[key] = loop                               # most recently used last
     while len(cache) > MAX_CACHED_LOOPS:
@@ -37,10 +65,16 @@ def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, traini
 
 def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler,
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
-                  disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None):
+                  disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
+                  inpaint_mask=None, paste_back=True):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
-    global batch once and hands each rank its slice."""
+    global batch once and hands each rank its slice.
+
+    Keyword-only, beyond the reference: ``strength`` in (0, 1] (with ``from_noised_image`` or ``inpaint_mask``): only the last
+    ``int(timesteps * strength)`` steps run, from the image noised to the first of them; 1.0 is the reference's ``from_noised_image``.
+    ``inpaint_mask`` (B or 1, 1, H, W) in [0, 1] at the resolution of ``example["pixel_values"]``, 1 = regenerate: starts from the noised image
+    and keeps the latents outside the mask on the image's.  ``paste_back``: outside the mask the returned pixels are ``pixel_values`` themselves."""
     if training_mode and torch.is_grad_enabled():
         # the reference back-propagates through the last denoising step (infer.py:99).  Here that differentiated call is a static
         # forward + backward plan, not a dynamic autograd graph: train.TrainStep(face_loss=..., vae=...) replays exactly this function
@@ -70,12 +104,21 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         generator = torch.manual_seed(seed)
         noise = torch.randn(shape, generator=generator).to(device)
 
-    if from_noised_image:                                                                 # :62-65
+    inpaint = inpaint_mask is not None
+    start = strength_start(timesteps, float(strength))
+    if start and not (from_noised_image or inpaint):
+        raise ValueError("strength < 1 needs an image to start from: from_noised_image=True or an inpaint_mask")
+    if inpaint:
+        pixel_mask, lat_mask = latent_mask(inpaint_mask, batch, latent_size)
+        if tuple(pixel_mask.shape[2:]) != tuple(example["pixel_values"].shape[2:]):
+            raise ValueError(f"inpaint_mask is {tuple(pixel_mask.shape[2:])}, pixel_values {tuple(example['pixel_values'].shape[2:])}")
+    if from_noised_image or inpaint:                                                      # :62-65
         if vae is None or not hasattr(vae, "encode"):
-            raise NotImplementedError("from_noised_image needs a vae with .encode (photoverse_amd.vae.AutoencoderKL)")
+            raise NotImplementedError(("inpaint_mask" if inpaint else "from_noised_image") + " needs a vae with .encode (photoverse_amd.vae.AutoencoderKL)")
         latents0 = vae.encode(example["pixel_values"].to(device)).latent_dist.sample().detach() * vae.config.scaling_factor
         sch.set_timesteps(timesteps)
-        noise = sch.add_noise(latents0, noise, sch.timesteps[:1].repeat(latents0.shape[0]))     # :65
+        start_noise = noise
+        noise = sch.add_noise(latents0, start_noise, sch.timesteps[start:start + 1].repeat(latents0.shape[0]))     # :65 (start = 0)
 
     placeholder_idx = example["concept_placeholder_idx"].to(device)                       # :72-73
     pixel_values_clip = example["pixel_values_clip"].to(device)
@@ -96,9 +139,11 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                                           "concept_placeholder_idx": placeholder_idx})[0]
 
     loop = _loop_for(unet, batch, latent_size, encoder_hidden_states_image.shape[1], timesteps, guidance_scale, sch,     # :98-119
-                     training_mode=training_mode, fusion_seed=0 if seed is None else int(seed))
+                     training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint)
     loop.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
-    loop.reset(noise)
+    if inpaint:
+        loop.set_inpaint(lat_mask.to(device), latents0, start_noise)
+    loop.reset(noise, start)
     latents = loop.run().clone()
 
     if vae is None:
@@ -109,6 +154,16 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     _latents = rec.affine_rows(latents.contiguous(), inv)
     rec.run()
     images = vae.decode(_latents).sample                                                  # :122-123
+    if inpaint and paste_back:
+        # the photograph outside the (binarised) pixel mask, the decoded result inside, and the clamp of :122 - one launch
+        orig = example["pixel_values"].to(device=images.device, dtype=torch.float32).contiguous()
+        if images.shape != orig.shape:
+            raise ValueError(f"paste_back: the decoded images are {tuple(images.shape)}, pixel_values {tuple(orig.shape)}")
+        images = images.float().contiguous()
+        rec = Recorder(images.device)
+        rec.composite_clamp(images, orig, pixel_mask.to(images.device), -1.0, 1.0, out=images)
+        rec.run()
+        return images
     if images.is_cuda and images.dtype == torch.float32 and images.is_contiguous():
         rec = Recorder(images.device)
         rec.clamp_(images, -1.0, 1.0)

@@ -898,6 +898,29 @@ class Recorder:
         self._add(self.lib.pv_cfg_dpm_step, _ptr(eps_u), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
                   float(guidance), latents.numel())
 
+    def cfg_dpm_step_masked(self, eps_u, eps_c, latents, x0_prev, coef, state, guidance, mask, known, noise):
+        """``cfg_dpm_step`` + the inpainting blend ``latents = m * x_next + (1 - m) * (q0 * known + q1 * noise)`` in the same launch; latents /
+        known / noise fp32 (B, C, H, W) contiguous, mask fp32 (B, 1, H, W), (q0, q1) = columns 5, 6 of the coefficient row."""
+        B, ch = latents.shape[0], latents.shape[1]
+        hw = latents.numel() // (B * ch)
+        assert mask.numel() == B * hw and known.shape == latents.shape and noise.shape == latents.shape, (mask.shape, known.shape, noise.shape, latents.shape)
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (latents, mask, known, noise))
+        self.keep.extend((eps_u, eps_c, latents, x0_prev, coef, state, mask, known, noise))
+        self._add(self.lib.pv_cfg_dpm_step_masked, _ptr(eps_u), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
+                  float(guidance), _ptr(mask), _ptr(known), _ptr(noise), ch, hw, latents.numel())
+
+    def composite_clamp(self, gen, orig, mask, lo, hi, out=None):
+        """out = clamp(m * gen + (1 - m) * orig, lo, hi); gen / orig fp32 (B, C, H, W) contiguous, mask fp32 (B, 1, H, W); ``out`` may be ``gen``."""
+        B, ch = gen.shape[0], gen.shape[1]
+        hw = gen.numel() // (B * ch)
+        if out is None:
+            out = self.empty(tuple(gen.shape), torch.float32)
+        assert mask.numel() == B * hw and orig.shape == gen.shape and out.shape == gen.shape, (mask.shape, orig.shape, gen.shape)
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (gen, orig, mask, out))
+        self.keep.extend((gen, orig, mask, out))
+        self._add(self.lib.pv_composite_clamp_f32, _ptr(gen), _ptr(orig), _ptr(mask), _ptr(out), float(lo), float(hi), B, ch, hw)
+        return out
+
     def fusion_draw(self, state, rng, forced, out, *, n_layers, rule1, rule2, scale, only_last_step):
         """Device-side grad-mode fusion draw (attention_processor.py:413-420 without the host sync): fills out[n_layers][2]."""
         self.keep.extend(t for t in (state, rng, forced, out) if t is not None)

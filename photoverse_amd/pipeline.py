@@ -31,7 +31,7 @@ class DenoiseLoop:
     def __init__(self, unet, batch: int, latent_size: int, n_ip: int, num_steps: int, guidance_scale: float,
                  scheduler: Optional[DPMSolverMultistepScheduler] = None, n_text: int = 77, use_graph: bool = True,
                  two_streams: bool = True, batch_splits: int = 1, training_mode: bool = False, fusion_seed: int = 0,
-                 merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None):
+                 merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False):
         """``training_mode``: the reference enables grad on the LAST denoising step only (infer.py:99), where every cross-attention
         layer of both forwards then draws its branch fusion (attention_processor.py:413-420).  Here the draw runs on the device inside
         the captured step (``pv_fusion_draw`` keyed on the step counter), so the same graph serves all steps.  This is the forward semantics
@@ -45,7 +45,12 @@ class DenoiseLoop:
         ``share_prefix`` (default: env ``PV_SHARE_PREFIX``, off - the headline metric counts two FULL forwards per step): conv_in, the first ResnetBlock and the first
         transformer block up to its self-attention never see the conditioning, so the uncond and cond forwards of a step compute them twice on
         identical inputs.  With ``share_prefix`` they are one plan whose outputs both branches start from - bit-identical latents, 2.5 % fewer
-        flops per step.  Reported by ``bench.py`` as a separately labelled number."""
+        flops per step.  Reported by ``bench.py`` as a separately labelled number.
+
+        ``inpaint`` (beyond the reference; [EXT] diffusers' inpainting with a 4-channel UNet): the solver step of the tail becomes
+        ``pv_cfg_dpm_step_masked`` - still one launch - which keeps the latents where ``mask`` is 0 on ``known`` noised with ``noise`` to the step's
+        next timestep (the clean ``known`` after the last step).  The three static buffers are filled by ``set_inpaint``; a mask of ones (the
+        initial content) is the plain loop."""
         dev = unet.device
         if dev.type != "cuda":
             raise RuntimeError("DenoiseLoop needs the UNet on a HIP device (no CPU path)")
@@ -61,7 +66,9 @@ class DenoiseLoop:
         self.latents = torch.zeros((batch, cfg.in_channels, latent_size, latent_size), dtype=f32, device=dev)
         self.x0_prev = torch.zeros_like(self.latents)
         self.timesteps = sch.timesteps.to(device=dev, dtype=f32)
-        self.coef = sch.coefficient_table().to(dev)
+        self.inpaint = bool(inpaint)
+        self._start = 0
+        self.coef = sch.coefficient_table(0, blend=self.inpaint).to(dev)
         self.state = torch.tensor([0, num_steps, 0, 0], dtype=torch.int32, device=dev)   # {step index, table rows, -, -}
         self._state0 = self.state.clone()
         self._host_step = 0
@@ -136,7 +143,14 @@ class DenoiseLoop:
                                               ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_c[sl], **kw, **fs2))
         self.eng_u, self.eng_c = self.engines_u[0], self.engines_c[0]
         self.tail = Recorder(dev)
-        self.tail.cfg_dpm_step(self.eps_u, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance)
+        if self.inpaint:
+            self.mask = torch.ones((batch, 1, latent_size, latent_size), dtype=f32, device=dev)
+            self.known = torch.zeros_like(self.latents)
+            self.noise = torch.zeros_like(self.latents)
+            self.tail.cfg_dpm_step_masked(self.eps_u, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
+                                          self.mask, self.known, self.noise)
+        else:
+            self.tail.cfg_dpm_step(self.eps_u, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance)
         self.tail.step_advance(self.state)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.use_graph = use_graph
@@ -161,12 +175,29 @@ class DenoiseLoop:
         for e in self.all_engines:
             e.run_conditioning()
 
-    def reset(self, noise: torch.Tensor):
-        """latents = noise * init_noise_sigma (``infer.py:70``); step counter to 0."""
+    def set_inpaint(self, mask: torch.Tensor, known: torch.Tensor, noise: torch.Tensor):
+        """Fill the static buffers of an ``inpaint`` loop: ``mask`` (B or 1, 1, S, S), 1 = regenerate; ``known`` (B, C, S, S) the latents to keep;
+        ``noise`` (B, C, S, S) the noise they are re-noised with at every step.  Contents only: the captured graph stays valid."""
+        if not self.inpaint:
+            raise RuntimeError("DenoiseLoop.set_inpaint(): the loop was built without inpaint=True")
+        for src, dst, what in ((mask, self.mask, "mask"), (known, self.known, "known latents"), (noise, self.noise, "noise")):
+            require_cuda(src, what)
+            dst.copy_(src.to(torch.float32).expand(dst.shape))
+
+    def reset(self, noise: torch.Tensor, start: int = 0):
+        """latents = noise * init_noise_sigma (``infer.py:70``); step counter to ``start`` (0: the whole schedule; > 0: the last ``T - start`` steps
+        of it, ``noise`` then being latents already at ``timesteps[start]``'s noise level)."""
+        start = int(start)
+        if not 0 <= start < self.T:
+            raise ValueError(f"DenoiseLoop.reset(): start {start} is outside the schedule of {self.T} steps")
+        if start != self._start:
+            # the row the loop begins at has no history: it is the table's first-order row.  Same buffer, so a captured graph keeps reading it
+            self.coef.copy_(self.scheduler.coefficient_table(start, blend=self.inpaint))
+            self._start = start
         self.latents.copy_(noise.to(self.latents.device) * self.scheduler.init_noise_sigma)
         self.x0_prev.zero_()
-        self.state.copy_(self._state0)
-        self._host_step = 0
+        self.state.copy_(self._state0 if start == 0 else torch.tensor([start, self.T, 0, 0], dtype=torch.int32))
+        self._host_step = start
 
     def _step_eager(self):
         for e in self.engines_p:                       # the conditioning-independent prefix both branches start from (share_prefix)
@@ -247,7 +278,7 @@ class DenoiseLoop:
             self._step_eager()
 
     def run(self, steps: Optional[int] = None) -> torch.Tensor:
-        for _ in range(self.T if steps is None else steps):
+        for _ in range(self.T - self._start if steps is None else steps):
             self.step()
         return self.latents
 
@@ -306,6 +337,8 @@ class PhotoVersePipeline:
             n = example["pixel_values_clip"].shape[0]
             sl = shard_batch(n, rank, world)
             local = {k: (v[sl] if torch.is_tensor(v) and v.shape[:1] == (n,) else v) for k, v in example.items()}
+            if torch.is_tensor(kw.get("inpaint_mask")) and kw["inpaint_mask"].shape[:1] == (n,):
+                kw["inpaint_mask"] = kw["inpaint_mask"][sl]                      # a per-sample mask goes with its samples; a (1, ...) mask is shared
             if kw.get("seed") is not None:
                 # the noise of the GLOBAL batch is drawn once with the reference's generator semantics (infer.py:52-59: CPU global
                 # generator) on every rank and sliced, so sample i equals sample i of the seeded 1-GPU run

@@ -61,12 +61,15 @@ class DPMSolverMultistepScheduler:
         shape = (-1, *([1] * (original_samples.dim() - 1)))
         return ca.view(shape).to(original_samples) * original_samples + cb.view(shape).to(original_samples) * noise
 
-    def coefficient_table(self) -> torch.Tensor:
-        """float32 [n, 8] rows {ca, cb, cx, c0, c1, 0, 0, 0} with, per step i (s = current, t = next sigma):
+    def coefficient_table(self, start: int = 0, blend: bool = False) -> torch.Tensor:
+        """float32 [n, 8] rows {ca, cb, cx, c0, c1, q0, q1, 0} with, per step i (s = current, t = next sigma):
             x0     = ca*x + cb*eps            ca = 1/alpha_s, cb = -sigma_s/alpha_s
             x_next = cx*x + c0*x0 + c1*x0_prev
         first order (first step, last step):  cx = sig_t/sig_s, c0 = -alpha_t*(exp(-h)-1), c1 = 0
         second order (midpoint):              c0 = -c*(1 + 1/(2 r0)), c1 = c/(2 r0),  c = alpha_t*(exp(-h)-1)
+        ``start``: the row the loop begins at (img2img strength): it has no history before it, so it is the first-order one instead of row 0.
+        ``blend``: q0 = alpha_t, q1 = sigma_t - the known latents of an inpainting run noised to the NEXT step, ``pv_cfg_dpm_step_masked``'s
+        ``k = q0*known + q1*noise`` ((1, 0) on the last row: the clean latents); 0, 0 otherwise.
         """
         n = self.num_inference_steps
         sig = self.sigmas.astype(np.float64)
@@ -81,13 +84,15 @@ class DPMSolverMultistepScheduler:
             c = a_t * (np.exp(-h) - 1.0)
             # first step (no history) and last step (final sigma 0 -> lower_order_final) are 1st order; with
             # solver_order 2 every other step is the 2nd-order multistep update
-            first = i == 0 or i == n - 1
+            first = i <= start or i == n - 1        # rows before ``start`` never run
             tab[i, 0], tab[i, 1], tab[i, 2] = 1.0 / a_s, -s_s / a_s, s_t / s_s
             if first:
                 tab[i, 3], tab[i, 4] = -c, 0.0
             else:
                 r0 = (lam[i] - lam[i - 1]) / h
                 tab[i, 3], tab[i, 4] = -c * (1.0 + 0.5 / r0), 0.5 * c / r0
+            if blend:
+                tab[i, 5], tab[i, 6] = a_t, s_t
         return torch.from_numpy(tab.astype(np.float32))
 
 
@@ -103,7 +108,9 @@ class DDIMScheduler(DPMSolverMultistepScheduler):
     is False for SD-v1.5 -> alphas_cumprod[0]).
     """
 
-    def coefficient_table(self) -> torch.Tensor:
+    def coefficient_table(self, start: int = 0, blend: bool = False) -> torch.Tensor:
+        """``start`` changes nothing here (no history: every row is first order); ``blend``: q0 = sqrt(a_p), q1 = sqrt(1 - a_p) of the row's own
+        a_p, (1, 0) on the last row."""
         n = self.num_inference_steps
         T = self.config["num_train_timesteps"]
         ratio = T // n
@@ -117,6 +124,8 @@ class DDIMScheduler(DPMSolverMultistepScheduler):
             r = np.sqrt(1 - a_p) / np.sqrt(1 - a_t)
             tab[i, 0], tab[i, 1] = 1.0 / np.sqrt(a_t), -np.sqrt(1 - a_t) / np.sqrt(a_t)
             tab[i, 2], tab[i, 3], tab[i, 4] = r, np.sqrt(a_p) - np.sqrt(a_t) * r, 0.0
+            if blend:
+                tab[i, 5], tab[i, 6] = (np.sqrt(a_p), np.sqrt(1 - a_p)) if i < n - 1 else (1.0, 0.0)
         return torch.from_numpy(tab.astype(np.float32))
 
     def set_timesteps(self, n: int):
