@@ -344,7 +344,7 @@ def ref_attention(p, v):
             lse[b * H + h], lerr[b * H + h] = l / LN2, le / LN2 + 2 * U32 * (l / LN2).abs()
     res = {"out": expect(out, det, F16, sig, CAP["attention"])}
     if "lse" in v:
-        res["lse"] = Expect(lse, lerr + store_bound(lse, F32), 0.0, F32)
+        res["lse"] = expect(lse, lerr, F32)      # its terms are worst-case ones (det): the same element bound, and ||lerr|| / ||lse|| in aggregate
     return res
 
 
@@ -545,10 +545,14 @@ def ref_row_gemm(p, v):
     w = f64(v["w"])
     det_in = sig_in = None
     if p.ln:
+        raw = x
         mean = x.mean(1, keepdim=True)
         rstd = 1.0 / torch.sqrt(((x - mean) ** 2).mean(1, keepdim=True) + float(p.ln_eps))
         x = (x - mean) * rstd
-        det_in = 2 * gamma(p.K) * x.abs()                             # fp32 row statistics
+        # fp32 row statistics: relative gamma(K) on mean and variance -> 2 gamma(K) |x_norm|; and the mean's ABSOLUTE error gamma(K) mean|x|
+        # (+ the two roundings of x * rstd - mean * rstd) times rstd, which is what remains when x - mean cancels (a constant row: x_norm = 0,
+        # rstd = eps^-1/2) - the same term ref_layernorm and the LayerNorm fold of ref_gemm carry
+        det_in = 2 * gamma(p.K) * x.abs() + rstd * (gamma(p.K) + 2 * U32) * raw.abs().mean(1, keepdim=True)
         sig_in = U16 * x.abs() + SUB16                                # rows normalised in registers, rounded to fp16 for the MFMA
     elif "x_norm" in v:
         tab = f64(v["x_norm"]).reshape(-1, 2, p.K)
@@ -779,6 +783,31 @@ def ref_cfg(a, v):
     return {"latents": Expect(xn, 8 * U32 * mx + 2.0 ** -140, 0.0, F32), "x0_prev": Expect(x0, 4 * U32 * mx0 + 2.0 ** -140, 0.0, F32)}
 
 
+def layout_cfg_masked(a):
+    L = layout_cfg(a)
+    L.update(mask=Buf(F32, a.n // (a.channels * a.hw), a.hw, a.hw), known=Buf(F32, 1, a.n, 0), noise=Buf(F32, 1, a.n, 0))
+    return L
+
+
+def ref_cfg_masked(a, v):
+    """pv_cfg_dpm_step's update x', then latents = m x' + (1 - m) k with k = q0 known + q1 noise, (q0, q1) = columns 5, 6 of the coefficient
+    row and m [B][1][hw] broadcast over the channels; x0_prev receives the unblended x0.  fp32 roundings: k is two products and a sum
+    (2 U32 M(k), M the sum of magnitudes), which the blend scales by |1 - m|; the blend itself rounds 1 - m, both products and the sum: at
+    most 3 U32 (|m| |x'| + |1 - m| M(k)); x' 's own error e(x') passes scaled by |m|."""
+    res = ref_cfg(a, v)
+    c = v["coef"].reshape(-1).double().cpu().tolist()
+    q0, q1 = c[5], c[6]
+    B = a.n // (a.channels * a.hw)
+    m = f64(v["mask"]).reshape(B, 1, a.hw).expand(B, a.channels, a.hw).reshape(1, -1)
+    kn, nz = f64(v["known"]), f64(v["noise"])
+    k = q0 * kn + q1 * nz
+    mk = abs(q0) * kn.abs() + abs(q1) * nz.abs()
+    xn, ex = res["latents"].ref, res["latents"].bound
+    mag = m.abs() * (xn.abs() + ex) + (1 - m).abs() * mk
+    res["latents"] = Expect(m * xn + (1 - m) * k, m.abs() * ex + 2 * U32 * (1 - m).abs() * mk + 3 * U32 * mag + 2.0 ** -140, 0.0, F32)
+    return res
+
+
 def layout_step_advance(a):
     return {"state": Buf(I32, 1, 1, 1, "inout")}
 
@@ -843,6 +872,7 @@ ARGS = {
     "pv_conv_out": ("x", "w", "bias", "out", "batch", "cin", "h", "wd", "cout"),
     "pv_timestep_embedding": ("timesteps", "state", "rows", "dim", "out"),
     "pv_cfg_dpm_step": ("eps_uncond", "eps_cond", "latents", "x0_prev", "coef", "state", "guidance", "n"),
+    "pv_cfg_dpm_step_masked": ("eps_uncond", "eps_cond", "latents", "x0_prev", "coef", "state", "guidance", "mask", "known", "noise", "channels", "hw", "n"),
     "pv_step_advance": ("state",),
     "pv_pointwise_nchw": ("x", "w", "bias", "out", "batch", "cin", "cout", "hw"),
     "pv_softmax_rows": ("x", "ld", "rows", "cols", "scale"),
@@ -857,7 +887,7 @@ LAYOUT = {
     "pv_groupnorm_stats_from_colstats": layout_gn_stats, "pv_groupnorm_scale_shift": layout_gn_scale_shift, "pv_groupnorm_apply": layout_gn_apply,
     "pv_im2col3x3": layout_im2col, "pv_conv_out": layout_conv_out, "pv_timestep_embedding": layout_timestep, "pv_cfg_dpm_step": layout_cfg,
     "pv_step_advance": layout_step_advance, "pv_pointwise_nchw": layout_pointwise, "pv_softmax_rows": layout_softmax_rows,
-    "pv_posterior_sample": layout_posterior,
+    "pv_posterior_sample": layout_posterior, "pv_cfg_dpm_step_masked": layout_cfg_masked,
 }
 
 REF = {
@@ -866,7 +896,7 @@ REF = {
     "pv_groupnorm_stats": ref_gn_stats, "pv_groupnorm_stats_from_colstats": ref_gn_stats, "pv_groupnorm_scale_shift": ref_gn_scale_shift,
     "pv_groupnorm_apply": ref_gn_apply, "pv_im2col3x3": ref_im2col, "pv_conv_out": ref_conv_out, "pv_timestep_embedding": ref_timestep,
     "pv_cfg_dpm_step": ref_cfg, "pv_step_advance": ref_step_advance, "pv_pointwise_nchw": ref_pointwise, "pv_softmax_rows": ref_softmax_rows,
-    "pv_posterior_sample": ref_posterior,
+    "pv_posterior_sample": ref_posterior, "pv_cfg_dpm_step_masked": ref_cfg_masked,
 }
 
 #: struct fields no layout / reference reads, and why.  Every other field of an audited struct is read by its layout or its reference

@@ -1,0 +1,792 @@
+"""Edge-case catalogue of the inference launchers: every kernel ``pv_gemm_conv`` / ``pv_attention`` can dispatch to, and every other inference
+launcher, at the smallest ragged shape that still selects it, audited element by element by ``oracle.plan_audit.Auditor``.
+
+A case is a name, a function that records one or a few launches on a fresh ``EdgeRecorder`` with seeded inputs, and the per-call environment
+switches that have to be set while it is recorded AND while it runs (the library reads them per call).  Shapes that depend on a dispatch threshold
+are found by asking ``pv_gemm_conv_kernel_info`` / ``pv_attention_kernel_info`` (``first``), not by restating the rule.
+
+Every tensor a launch addresses is a guarded view (``guarded_out`` / ``guarded_in``): it sits in the middle of a larger storage with at least
+``TILE_ROWS`` = 256 rows x ld elements in front and behind (256 rows: the tallest tile of the library, so a whole stray tile stays inside the
+storage the Auditor snapshots), and with a row gap (``ld = cols + 8``) wherever the launcher takes a leading dimension.  Output margins hold the
+byte ``OUT_FILL``; input margins and row gaps hold NaN (0x7fffffff next to integers): an input's described extent is all a launch may depend
+on, so anything read outside it that reaches a result makes the result non-finite, which the Auditor's finite check reports.  Reads inside an
+arena cannot fault.  ``EdgeRecorder.empty`` guards the buffers the recorder allocates itself (workspaces, statistics, outputs), ``reguard`` the
+inputs it derives at record time (folded weights, row sums).
+
+With a CPU device the recorder is dry: it builds the same parameter blocks and tags (the ``*_kernel_info`` calls need no GPU) and never runs.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+import math
+import os
+import zlib
+from dataclasses import dataclass, field
+from typing import Callable, Dict, List, Optional
+
+import torch
+
+from . import abi_ref as A
+from .plan_audit import Params
+
+F16, F32, I32 = torch.float16, torch.float32, torch.int32
+TILE_ROWS = 256
+OUT_FILL = 0xA5
+FLAT_CAP = 4096          # a buffer without rows (ld 0) is guarded by 256 x min(its length, FLAT_CAP) elements
+
+
+def _isz(dt) -> int:
+    return torch.empty((), dtype=dt).element_size()
+
+
+def _arena(n_front: int, n_body: int, dtype, device, fill, arenas):
+    total = n_front + n_body + n_front
+    if fill == "out":
+        a = torch.empty(total, dtype=dtype, device=device)
+        a.view(torch.uint8).fill_(OUT_FILL)
+    elif dtype.is_floating_point:
+        a = torch.full((total,), float("nan"), dtype=dtype, device=device)
+    else:
+        a = torch.full((total,), torch.iinfo(dtype).max, dtype=dtype, device=device)
+    if arenas is not None:
+        arenas.append((a.data_ptr(), a.data_ptr() + total * _isz(dtype), a))
+    return a
+
+
+def guarded_out(rows: int, cols: int, dtype=F16, ld: Optional[int] = None, *, device="cpu", arenas=None) -> torch.Tensor:
+    """A [rows, cols] view (row stride ``ld``, default ``cols``) with >= 256 x ld elements of ``OUT_FILL`` bytes in front and behind."""
+    ld = cols if ld is None else ld
+    assert ld >= cols, (cols, ld)
+    m = TILE_ROWS * ld
+    a = _arena(m, rows * ld, dtype, device, "out", arenas)
+    return a[m:m + rows * ld].view(rows, ld)[:, :cols]
+
+
+def guarded_in(t: torch.Tensor, ld: Optional[int] = None, *, device="cpu", arenas=None) -> torch.Tensor:
+    """``t`` placed the same way, margins and row gaps NaN (integers: the largest value).  2-D: a row view with stride ``ld``; any other rank:
+    contiguous, guarded by 256 x min(numel, FLAT_CAP) elements."""
+    if t.dim() == 2:
+        rows, cols = t.shape
+        ld = cols if ld is None else ld
+        m = TILE_ROWS * ld
+        a = _arena(m, rows * ld, t.dtype, device, "in", arenas)
+        v = a[m:m + rows * ld].view(rows, ld)[:, :cols]
+    else:
+        n = t.numel()
+        m = TILE_ROWS * min(max(n, 1), FLAT_CAP)
+        a = _arena(m, n, t.dtype, device, "in", arenas)
+        v = a[m:m + n].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+def _recorder_base():
+    from photoverse_amd.ops import Recorder
+    return Recorder
+
+
+def make_recorder(device):
+    Recorder = _recorder_base()
+
+    class EdgeRecorder(Recorder):
+        """``ops.Recorder`` whose own allocations are guarded; dry (records, never runs) on a CPU device."""
+
+        def __init__(self, dev):
+            super().__init__(torch.device("cuda"))          # touches no device: loads the library and sets the lists
+            self.device = torch.device(dev)
+            self.dry = self.device.type != "cuda"
+            self.arenas: list = []
+
+        def empty(self, shape, dtype=F16):
+            shape = (shape,) if isinstance(shape, int) else tuple(shape)
+            n = math.prod(shape)
+            row = min(max(n, 1), FLAT_CAP) if len(shape) == 1 else (shape[-1] if len(shape) == 2 else shape[-1] * shape[-2])
+            m = TILE_ROWS * row
+            a = _arena(m, n, dtype, self.device, "out", self.arenas)
+            self.bytes_allocated += n * _isz(dtype)
+            self.keep.append(a)
+            return a[m:m + n].view(shape)
+
+        def run(self, stream=None):
+            if self.dry:
+                raise RuntimeError("a dry EdgeRecorder holds host pointers: it describes launches, it cannot run them")
+            return super().run(stream)
+
+    return EdgeRecorder(device)
+
+
+class Ctx:
+    """What a case function gets: the recorder, a seeded generator and the guarded allocators."""
+
+    def __init__(self, name: str, device):
+        self.rec = make_recorder(device)
+        self.dev = self.rec.device
+        self.g = torch.Generator().manual_seed(zlib.crc32(name.encode()) & 0x7FFFFFFF)
+
+    def randn(self, *shape, scale=1.0):
+        return torch.randn(*shape, generator=self.g) * scale
+
+    def put(self, t: torch.Tensor, ld: Optional[int] = None) -> torch.Tensor:
+        v = guarded_in(t, ld, device=self.dev, arenas=self.rec.arenas)
+        self.rec.keep.append(v)
+        return v
+
+    def h(self, rows, cols, scale=1.0, gap=8):
+        """fp16 rows of N(0, scale^2) with a row gap."""
+        return self.put(self.randn(rows, cols, scale=scale).to(F16), cols + gap)
+
+    def w(self, n, k):
+        """a contiguous fp16 weight [n][k] of N(0, 1 / k)"""
+        return self.put(self.randn(n, k, scale=k ** -0.5).to(F16))
+
+    def f(self, *shape, scale=1.0, shift=0.0):
+        return self.put(self.randn(*shape, scale=scale) + shift)
+
+    def out(self, rows, cols, dtype=F16, gap=8):
+        v = guarded_out(rows, cols, dtype, cols + gap, device=self.dev, arenas=self.rec.arenas)
+        self.rec.keep.append(v)
+        return v
+
+    def out_flat(self, *shape, dtype=F32):
+        return self.rec.empty(shape, dtype) if len(shape) == 1 else self.rec.empty((math.prod(shape),), dtype).view(shape)
+
+    def colstats_for(self, x: torch.Tensor):
+        """The column statistics a GEMM epilogue leaves for its contiguous fp16 output ``x`` ([ceil(M/64)][2][N] fp32 sums and sums of squares
+        per 64-row block), computed here so that a consumer can be driven without its producer."""
+        M, N = x.shape
+        nb = (M + 63) // 64
+        xf = torch.cat([x.float().cpu(), torch.zeros(nb * 64 - M, N)]).view(nb, 64, N)
+        cs = self.put(torch.stack([xf.sum(1), (xf * xf).sum(1)], 1).contiguous())
+        self.rec.colstats[(x.data_ptr(), M, N)] = cs
+        return cs
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ the registry
+@dataclass
+class Case:
+    name: str
+    fn: Callable
+    env: Dict[str, str] = field(default_factory=dict)
+    expect: tuple = ()          # kernel symbols this case exists for: each must be among its tags
+
+
+CASES: List[Case] = []
+
+
+def add(name, fn, env=None, expect=()):
+    CASES.append(Case(name, fn, dict(env or {}), tuple(expect)))
+
+
+@contextlib.contextmanager
+def environment(env: Dict[str, str], folds: bool = True):
+    """The per-call switches of a case, and the recorder's two opt-in folds (``Recorder.GEMM_LN`` / ``GN_FOLD``, off by default) enabled."""
+    Recorder = _recorder_base()
+    old = {k: os.environ.get(k) for k in env}
+    oldf = (Recorder.GEMM_LN, Recorder.GN_FOLD)
+    os.environ.update(env)
+    if folds:
+        Recorder.GEMM_LN = Recorder.GN_FOLD = True
+    try:
+        yield
+    finally:
+        Recorder.GEMM_LN, Recorder.GN_FOLD = oldf
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def build(c: Case, device="cpu"):
+    """Record the case on a fresh recorder (inside ``environment(c.env)``: the caller keeps it set while the launches run)."""
+    ctx = Ctx(c.name, device)
+    c.fn(ctx)
+    reguard(ctx)
+    return ctx.rec
+
+
+def first(pred, candidates):
+    for x in candidates:
+        if pred(x):
+            return x
+    raise ValueError("no candidate selects the wanted kernel")
+
+
+def gemm_symbol(**fields) -> str:
+    return _recorder_base()._probe_gemm(**fields)
+
+
+def attn_symbol(**fields) -> str:
+    from photoverse_amd import _lib
+    p = _lib.AttnParams()
+    for k in ("q", "k", "v", "out"):
+        setattr(p, k, 0x1000)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    try:
+        return _lib.kernel_info(_lib.load().pv_attention_kernel_info, p)[0]
+    except ValueError:
+        return ""
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ guard checks
+def _call_params(fn, args):
+    name = fn.__name__
+    if args and isinstance(args[0], type(C.byref(C.c_int()))):
+        return name, Params(args[0]._obj, dict(zip(A.ARGS.get(name, ()), args[1:]))), args[0]._obj
+    return name, Params(None, dict(zip(A.ARGS[name], args))), None
+
+
+def _in_arena(arenas, addr, nbytes, margin):
+    for lo, hi, _ in arenas:
+        if lo <= addr < hi:
+            return addr - lo >= margin and hi - (addr + nbytes) >= margin
+    return False
+
+
+def _extent(buf: A.Buf):
+    isz = _isz(buf.dtype)
+    ld = buf.ld if buf.ld else buf.cols
+    ext = ((buf.rows - 1) * ld + buf.cols) * isz if buf.rows > 0 and buf.cols > 0 else 0
+    margin = TILE_ROWS * (buf.ld if buf.ld else min(buf.cols, FLAT_CAP)) * isz
+    return ext, margin
+
+
+def unguarded(rec) -> List[str]:
+    """Every pointer of every recorded call that is NOT a guarded view of its described extent (empty = the catalogue's placement rule holds)."""
+    bad = []
+    for i, (fn, args) in enumerate(rec.calls):
+        name, p, _ = _call_params(fn, args)
+        for k, buf in A.LAYOUT[name](p).items():
+            addr = getattr(p, k)
+            if not addr:
+                continue
+            buf = buf if buf is not None else A.Buf(F32, 1, 8, 0)          # extent known from device state only: its first row
+            ext, margin = _extent(buf)
+            if not _in_arena(rec.arenas, addr, ext, margin):
+                bad.append(f"call {i} ({name}), field {k}")
+    return bad
+
+
+def reguard(ctx: Ctx):
+    """Move the inputs the recorder derived at record time (LayerNorm-folded weights, bias folds, weight row sums) into guarded storage and
+    point the parameter block at the copy."""
+    rec = ctx.rec
+    held = [t for t in rec.keep if isinstance(t, torch.Tensor)]
+    for fn, args in rec.calls:
+        name, p, struct = _call_params(fn, args)
+        if struct is None:
+            continue
+        for k, buf in A.LAYOUT[name](p).items():
+            addr = getattr(p, k)
+            if not addr or buf is None or buf.role != "in":
+                continue
+            ext, margin = _extent(buf)
+            if _in_arena(rec.arenas, addr, ext, margin):
+                continue
+            src = None
+            for t in held:
+                s = t.untyped_storage()
+                if s.data_ptr() <= addr and addr + ext <= s.data_ptr() + s.nbytes() and t.dtype == buf.dtype:
+                    ld = buf.ld if buf.ld else buf.cols
+                    src = torch.empty(0, dtype=buf.dtype, device=t.device).set_(s, (addr - s.data_ptr()) // _isz(buf.dtype), (buf.rows, buf.cols), (ld, 1))
+                    break
+            if src is None:
+                raise AssertionError(f"{name}: field {k} addresses no tensor the recorder holds")
+            g = ctx.put(src.cpu().clone() if buf.rows > 1 else src.cpu().reshape(-1).clone(), None)
+            setattr(struct, k, g.data_ptr())
+
+
+# ============================================================================================================================== pv_gemm_conv
+def _linear(ctx, M, N, K, *, bias=False, rowadd=None, rpi=None, residual=False, act=0, out_f32=False, geglu=False, splitk=0, colstats=False,
+            dual=False, ln=False, a=None, wt=None, bias_t=None):
+    """One Linear launch.  ``rowadd``: "shared" / "image" (rows_per_image ``rpi``); ``dual``: two strided sources of K / 2 channels each."""
+    rec = ctx.rec
+    n_out = N // 2 if geglu else N
+    if a is None:
+        a = (ctx.h(M, K // 2), ctx.h(M, K // 2)) if dual else (ctx.h(M, K), None)
+    w = ctx.w(N, K) if wt is None else wt
+    kw = {}
+    if bias or bias_t is not None:
+        kw["bias"] = ctx.f(N) if bias_t is None else bias_t
+    if rowadd == "shared":
+        kw["rowadd"] = ctx.f(n_out)
+    elif rowadd == "image":
+        imgs = (M + rpi - 1) // rpi
+        ra = ctx.put(ctx.randn(imgs, n_out), n_out + 8)
+        kw.update(rowadd=ra, rowadd_ld=ra.stride(0), rows_per_image=rpi)
+    if residual:
+        kw["residual"] = ctx.h(M, n_out)
+    if ln:
+        kw.update(ln_gamma=ctx.f(K, scale=0.2, shift=1.0), ln_beta=ctx.f(K, scale=0.2))
+    out = ctx.out(M, n_out, F32 if out_f32 else F16, gap=0 if colstats else 8)       # column statistics need a contiguous output (ops.Recorder.gemm)
+    rec.gemm(a[0], w, a1=a[1], out=out, act=act, out_f32=out_f32, geglu=geglu, splitk=splitk, colstats=colstats, **kw)
+    return out
+
+
+def _conv(ctx, batch, hin, win, c0, N, *, c1=0, stride=1, up=0, pad=1, splitk=0, colstats=False, bias=True, rowadd=False, residual=False, act=0,
+          a_norm=None, a=None):
+    rec = ctx.rec
+    hl, wl = (hin * 2, win * 2) if up else (hin, win)
+    if stride == 2:          # Conv2d(stride=2, padding=1), or F.pad(x, (0, 1, 0, 1)) + Conv2d(stride=2, padding=0) when pad == 0: torch's output sizes
+        hout, wout = (hl + (2 if pad else 1) - 3) // 2 + 1, (wl + (2 if pad else 1) - 3) // 2 + 1
+    else:
+        hout, wout = hl, wl
+    M = batch * hout * wout
+    if a is None:
+        a = (ctx.h(batch * hin * win, c0), ctx.h(batch * hin * win, c1) if c1 else None)
+    w = ctx.w(N, 9 * (c0 + c1))
+    kw = {}
+    if bias:
+        kw["bias"] = ctx.f(N)
+    if rowadd:
+        ra = ctx.put(ctx.randn(batch, N), N + 8)
+        kw.update(rowadd=ra, rowadd_ld=ra.stride(0))
+    if residual:
+        kw["residual"] = ctx.h(M, N)
+    if a_norm is not None:
+        kw.update(a_norm=a_norm, a_norm_act=1)
+    out = ctx.out(M, N, F16, gap=0 if colstats else 8)
+    rec.gemm(a[0], w, a1=a[1], out=out, act=act, splitk=splitk, colstats=colstats,
+             conv=dict(batch=batch, hin=hin, win=win, hout=hout, wout=wout, stride=stride, upsample=up, pad=pad), **kw)
+    return out
+
+
+def _lin_fields(M, N, K, **kw):
+    f = dict(c0=K, lda0=K, N=N, ldc=N, M=M, taps=1, batch=1, hin=1, win=1, hout=M, wout=1, stride=1, pad=1)
+    f.update(kw)
+    return f
+
+
+G64 = "gemm_conv_kernel<%d, false, false, false, false, 2>"
+G128 = "gemm_conv_kernel<%d, false, false, false, false, 4>"
+
+# 64-row kernels: M in {1, 65}, N in {160, 128}, one K-step and three; every epilogue feature and activation once per tile family
+add("gemm64-n160-m1-k64-bias-silu-rowadd", lambda c: _linear(c, 1, 160, 64, bias=True, act=1, rowadd="shared"), expect=(G64 % 5,))
+add("gemm64-n160-m65-k192-rowadd-per-image-res-qgelu", lambda c: _linear(c, 65, 160, 192, rowadd="image", rpi=40, residual=True, act=2), expect=(G64 % 5,))
+add("gemm64-n160-m65-k128-dual-f32", lambda c: _linear(c, 65, 160, 128, dual=True, out_f32=True, bias=True), expect=(G64 % 5,))
+add("gemm64-n128-m1-k192-f32-leaky-bias", lambda c: _linear(c, 1, 128, 192, out_f32=True, act=3, bias=True), expect=(G64 % 4,))
+add("gemm64-n128-m65-k64-res-rowadd", lambda c: _linear(c, 65, 128, 64, residual=True, rowadd="shared", act=1), expect=(G64 % 4,))
+add("gemm64-n128-m65-k128-dual-rowadd-per-image-qgelu", lambda c: _linear(c, 65, 128, 128, dual=True, rowadd="image", rpi=40, act=2, bias=True), expect=(G64 % 4,))
+
+
+def _m_for_128_row_kernel(N, nf):
+    """Smallest M = 128 t + 65 whose launch count puts a plain Linear on the 128-row kernel (asked from the library)."""
+    return first(lambda M: gemm_symbol(**_lin_fields(M, N, 64)) == G128 % nf, (128 * t + 65 for t in range(0, 4096)))
+
+
+add("gemm128-n1280-by-count-bias-silu-rowadd-per-image", lambda c: _linear(c, _m_for_128_row_kernel(1280, 5), 1280, 64, bias=True, act=1, rowadd="image", rpi=100),
+    expect=(G128 % 5,))
+add("gemm128-n1024-by-count-res-leaky-f32", lambda c: _linear(c, _m_for_128_row_kernel(1024, 4), 1024, 64, residual=True, act=3, out_f32=True, rowadd="shared"),
+    expect=(G128 % 4,))
+for _sk, _n, _nf in ((2, 160, 5), (3, 128, 4), (3, 160, 5), (2, 128, 4)):
+    add(f"gemm128-splitk{_sk}-n{_n}-m130-k192-colstats", lambda c, sk=_sk, n=_n: _linear(c, 130, n, 192, splitk=sk, colstats=True, bias=True, act=1, residual=sk == 3),
+        expect=(G128 % _nf,))
+for _n, _nf in ((160, 5), (128, 4)):
+    add(f"gemm-colstats-n{_n}-m130", lambda c, n=_n: _linear(c, 130, n, 64, colstats=True, bias=True, act=1, rowadd="image", rpi=50),
+        expect=("gemm_conv_kernel<%d, false, false, true, false, 4>" % _nf,))
+add("gemm-geglu-n256-m130", lambda c: _linear(c, 130, 256, 64, geglu=True, bias=True), expect=("gemm_conv_kernel<4, false, true, false, false, 4>",))
+GEGLU_LOOP = "gemm_conv_kernel<4, false, true, false, true, 4>"
+
+
+def _geglu_loop(c):
+    M = first(lambda M: gemm_symbol(**_lin_fields(M, 256, 64, geglu=1, ldc=128)) == GEGLU_LOOP, (128 * t + 1 for t in range(0, 4096)))
+    _linear(c, M, 256, 64, geglu=True, bias=True)
+
+
+add("gemm-geglu-tile-loop-smallest-m", _geglu_loop, expect=(GEGLU_LOOP,))
+
+# 3x3 convs: batch 2, a 5 x 7 image, 64 channels
+C9 = "gemm_conv_kernel<%d, true, false, %s, false, 4>"
+add("conv-s1-n160-rowadd-silu", lambda c: _conv(c, 2, 5, 7, 64, 160, rowadd=True, act=1), expect=(C9 % (5, "false"),))
+add("conv-s1-n128-res", lambda c: _conv(c, 2, 5, 7, 64, 128, residual=True), expect=(C9 % (4, "false"),))
+add("conv-s2-pad1-n128", lambda c: _conv(c, 2, 5, 7, 64, 128, stride=2), expect=(C9 % (4, "false"),))
+add("conv-s2-pad0-n160", lambda c: _conv(c, 2, 5, 7, 64, 160, stride=2, pad=0), expect=(C9 % (5, "false"),))
+add("conv-up2-n128-res-silu", lambda c: _conv(c, 2, 5, 7, 64, 128, up=1, residual=True, act=1), expect=(C9 % (4, "false"),))
+add("conv-dual-n160", lambda c: _conv(c, 2, 5, 7, 64, 160, c1=64, rowadd=True), expect=(C9 % (5, "false"),))
+add("conv-dual-s2-pad1-n128", lambda c: _conv(c, 2, 5, 7, 64, 128, c1=64, stride=2), expect=(C9 % (4, "false"),))
+for _sk, _n, _nf in ((2, 160, 5), (3, 128, 4), (5, 160, 5), (8, 128, 4), (5, 128, 4), (8, 160, 5)):
+    add(f"conv-splitk{_sk}-n{_n}", lambda c, sk=_sk, n=_n: _conv(c, 2, 5, 7, 64, n, splitk=sk, colstats=sk in (2, 8), act=1), expect=(C9 % (_nf, "false"),))
+for _n, _nf in ((160, 5), (128, 4)):
+    add(f"conv-colstats-n{_n}", lambda c, n=_n: _conv(c, 2, 5, 7, 64, n, colstats=True, rowadd=True, act=1), expect=(C9 % (_nf, "true"),))
+
+# the 256-row tile (big_min = 1 puts a one-tile launch on it)
+BIG = "big_tile_kernel<%s, %s, 8, %d, %s>"
+
+
+def _big(fn):
+    def run(c):
+        c.rec.big_min = 1
+        fn(c)
+    return run
+
+
+for _cs in (False, True):
+    _t = "true" if _cs else "false"
+    add(f"big-linear-m257-k640-n320{'-colstats' if _cs else ''}", _big(lambda c, cs=_cs: _linear(c, 257, 320, 640, bias=True, act=1, residual=True, colstats=cs, rowadd="image", rpi=100)),
+        expect=(BIG % (_t, "false", 1, "false"),))
+    add(f"big-conv-gather-10x10{'-colstats' if _cs else ''}", _big(lambda c, cs=_cs: _conv(c, 1, 10, 10, 64, 320, colstats=cs, rowadd=True, act=1, residual=True)),
+        expect=(BIG % (_t, "false", 0, "false"),))
+    add(f"big-conv-upsample-5x5{'-colstats' if _cs else ''}", _big(lambda c, cs=_cs: _conv(c, 1, 5, 5, 64, 320, up=1, colstats=cs)), expect=(BIG % (_t, "true", 0, "false"),))
+    add(f"big-conv-patch64-4x64{'-colstats' if _cs else ''}", _big(lambda c, cs=_cs: _conv(c, 1, 4, 64, 64, 320, colstats=cs, rowadd=True, act=1, residual=True)),
+        expect=(BIG % (_t, "false", 3, "false"),))
+    add(f"big-conv-patch32-8x32{'-colstats' if _cs else ''}", _big(lambda c, cs=_cs: _conv(c, 1, 8, 32, 64, 320, colstats=cs, act=1)), env={"PV_CONV_PATCH": "1"},
+        expect=(BIG % (_t, "false", 4, "false"),))
+add("big-geglu-m257-k640-n256", _big(lambda c: _linear(c, 257, 256, 640, geglu=True, bias=True)), expect=(BIG % ("false", "false", 2, "false"),))
+add("big-linear-layernorm-fold", _big(lambda c: _linear(c, 257, 320, 640, ln=True, bias=True, act=1)), expect=(BIG % ("false", "false", 1, "true"),))
+add("big-geglu-layernorm-fold", _big(lambda c: _linear(c, 257, 256, 640, ln=True, geglu=True, bias=True)), expect=(BIG % ("false", "false", 2, "true"),))
+add("big-conv-splitk2-cin128", _big(lambda c: _conv(c, 1, 10, 10, 128, 320, splitk=2, colstats=True, act=1)), expect=(BIG % ("false", "false", 0, "false"),))
+add("big-conv-upsample-splitk2-cin128", _big(lambda c: _conv(c, 1, 5, 5, 128, 320, up=1, splitk=2)), expect=(BIG % ("false", "true", 0, "false"),))
+add("big-conv-patch64-batch2", _big(lambda c: _conv(c, 2, 4, 64, 64, 320, act=1)), expect=(BIG % ("false", "false", 3, "false"),))
+add("big-conv-patch64-dual", _big(lambda c: _conv(c, 1, 4, 64, 64, 320, c1=64, rowadd=True)), expect=(BIG % ("false", "false", 3, "false"),))
+add("big-conv-patch32-batch2-dual", _big(lambda c: _conv(c, 2, 8, 32, 64, 320, c1=64)), env={"PV_CONV_PATCH": "1"}, expect=(BIG % ("false", "false", 4, "false"),))
+
+
+def _gn_fold_conv(c, batch, h, w, c0, c1, colstats):
+    """pv_groupnorm_scale_shift on the raw tensors' column statistics, then the conv that normalises its LDS-resident patch with the table."""
+    c.rec.big_min = 1
+    x0 = c.put(c.randn(batch * h * w, c0, scale=1.5).add_(0.5).to(F16))
+    x1 = c.put(c.randn(batch * h * w, c1).to(F16)) if c1 else None
+    c.colstats_for(x0)
+    if c1:
+        c.colstats_for(x1)
+    tab = c.rec.groupnorm_table(x0, c.f(c0 + c1, scale=0.3, shift=1.0), c.f(c0 + c1, scale=0.2), batch=batch, hw=h * w, x1=x1)
+    assert tab is not None
+    _conv(c, batch, h, w, c0, 320, c1=c1, colstats=colstats, a_norm=tab, a=(x0, x1), act=1)
+
+
+for _cs in (False, True):
+    _t = "true" if _cs else "false"
+    add(f"big-conv-groupnorm-fold-patch64{'-colstats' if _cs else ''}", lambda c, cs=_cs: _gn_fold_conv(c, 1, 4, 64, 64, 0, cs), expect=(BIG % (_t, "false", 5, "false"),))
+    add(f"big-conv-groupnorm-fold-patch32{'-colstats' if _cs else ''}", lambda c, cs=_cs: _gn_fold_conv(c, 1, 8, 32, 64, 0, cs), env={"PV_CONV_PATCH": "1"},
+        expect=(BIG % (_t, "false", 6, "false"),))
+add("big-conv-groupnorm-fold-patch64-batch2-dual", lambda c: _gn_fold_conv(c, 2, 4, 64, 64, 64, False), expect=(BIG % ("false", "false", 5, "false"),))
+
+
+# ============================================================================================================================== pv_attention
+def _attention(ctx, batch, heads, nq, nk, d, *, causal=False, lse=False, sliced=True, hot_key=False, zero=False):
+    """q / k / v: column slices of one [rows][3 C + 8] buffer when nq == nk (the fused QKV GEMM's output), separate strided buffers otherwise."""
+    Cw = heads * d
+    if sliced and nq == nk:
+        qkv = ctx.randn(batch * nq, 3 * Cw)
+        if zero:
+            qkv.zero_()
+        buf = ctx.put(qkv.to(F16), 3 * Cw + 8)
+        q, k, v = buf[:, :Cw], buf[:, Cw:2 * Cw], buf[:, 2 * Cw:]
+    else:
+        qt, kt = ctx.randn(batch * nq, Cw), ctx.randn(batch * nk, Cw)
+        if hot_key:
+            # the queries share a unit offset and the last key of every image (in the last, partial key block) points along it with length 12:
+            # its score is 12 (+- 12 / sqrt d) against the other keys' ~1.4 sigma
+            qt += 1.0
+            for b in range(batch):
+                kt[b * nk + nk - 1] = 12.0 / math.sqrt(d)
+        q, k, v = ctx.put(qt.to(F16), Cw + 8), ctx.put(kt.to(F16), Cw + 8), ctx.h(batch * nk, Cw, gap=16)
+    out = ctx.out(batch * nq, Cw)
+    l = ctx.out_flat(batch, heads, nq) if lse else None
+    ctx.rec.attention(q, k, v, batch=batch, heads=heads, nq=nq, nk=nk, d=d, causal=causal, out=out, lse=l)
+
+
+def _attn_set(d):
+    def run(c):
+        for nq, nk, kw in ((1, 65, dict(lse=True)), (65, 1, {}), (130, 63, {}), (63, 64, dict(lse=True)), (65, 65, dict(causal=True, lse=True)), (77, 77, dict(causal=True)),
+                           (65, 65, {})):
+            _attention(c, 2, 2, nq, nk, d, **kw)
+    return run
+
+
+for _d in (64, 80, 160):
+    add(f"attention-d{_d}-ragged", _attn_set(_d), expect=(f"attn_kernel<{_d}, 2, false>",))
+add("attention-d40-ragged", _attn_set(40), expect=("attn_kernel<40, 2, true>",))
+A40_4 = "attn_kernel<40, 4, true>"
+
+
+def _bh_for_four_fragments(**kw):
+    return first(lambda bh: attn_symbol(batch=bh // 8, heads=8, nq=257, nk=257, d=40, ldq=968, ldk=968, ldv=968, ldo=328, **kw) == A40_4, range(8, 8192, 8))
+
+
+add("attention-d40-four-fragments-causal-nq257", lambda c: _attention(c, _bh_for_four_fragments(causal=1) // 8, 8, 257, 257, 40, causal=True, lse=True), expect=(A40_4,))
+add("attention-d40-four-fragments-nq257", lambda c: _attention(c, _bh_for_four_fragments() // 8, 8, 257, 257, 40), env={"PV_ATTN8": "-1"}, expect=(A40_4,))
+add("attention-d40-8wave-n600", lambda c: _attention(c, 1, 2, 600, 600, 40, lse=True), env={"PV_ATTN8_MIN": "1"}, expect=("attn8_kernel<497>",))
+add("attention-d40-8wave-nq600-nk77", lambda c: _attention(c, 1, 2, 600, 77, 40), env={"PV_ATTN8_MIN": "1"}, expect=("attn8_kernel<497>",))
+for _d in (40, 80):
+    add(f"attention-d{_d}-hot-key-in-the-partial-block", lambda c, d=_d: _attention(c, 2, 2, 130, 65, d, hot_key=True, lse=True))
+add("attention-d64-all-zero", lambda c: _attention(c, 1, 2, 65, 65, 64, zero=True, lse=True))
+
+
+# ============================================================================================================================== cross attention
+def _kv(ctx, batch, nt, nip, Cw):
+    return ctx.h(batch * nt, Cw), ctx.h(batch * nt, Cw, gap=16), (ctx.h(batch * nip, Cw) if nip else None), (ctx.h(batch * nip, Cw, gap=24) if nip else None)
+
+
+def _xattn(ctx, batch, heads, nq, nt, nip, d, *, vnorm=False, fusion=None):
+    Cw = heads * d
+    q = ctx.h(batch * nq, Cw)
+    kt, vt, kip, vip = _kv(ctx, batch, nt, nip, Cw)
+    vn = ctx.out_flat(batch, heads, nip) if vnorm else None
+    fu = ctx.put(torch.tensor(fusion, dtype=F32)) if fusion else None
+    ctx.rec.cross_attention(q, kt, vt, kip, vip, batch=batch, heads=heads, nq=nq, nt=nt, nip=nip, d=d, vnorm=vn, fusion=fu, out=ctx.out(batch * nq, Cw),
+                            w_text=1.0 if fusion is None else 7.0, w_ip=1.0 if fusion is None else 7.0)      # a device pair overrides the host weights
+
+
+for _i, _d in enumerate((40, 80, 160)):
+    for _j, (_nt, _nip) in enumerate(((1, 16), (77, 1), (80, 2))):
+        _fu = (None, (2.0, 0.0), (0.0, 2.0))[(_i + _j) % 3]
+        if _fu is not None and (_nt, _nip)[0 if _fu[0] else 1] == 1:      # keep the weight on the many-key branch: a one-key softmax is a copy
+            _fu = _fu[::-1]
+        add(f"xattn-d{_d}-nt{_nt}-nip{_nip}", lambda c, d=_d, nt=_nt, nip=_nip, vn=(_i + _j) % 2 == 0, fu=_fu: _xattn(c, 2, 2, 130, nt, nip, d, vnorm=vn, fusion=fu))
+    # xattn_kernel<D, true>: >= 2048 query tiles of 128 rows in the launch (pv_attn.hip keeps ~1024 workgroups): nq = 130 is two tiles per (image, head)
+    add(f"xattn-d{_d}-multi-tile", lambda c, d=_d: _xattn(c, 128, 8, 130, 77, 2, d, vnorm=True))
+
+
+def _lnq(ctx, batch, heads, d, nq, nt, nip, *, ln, vnorm=False, fusion=None):
+    Cw = heads * d
+    hs = ctx.put((ctx.randn(batch * nq, Cw) * 1.5 + 0.5).to(F16), Cw + 8)
+    kt, vt, kip, vip = _kv(ctx, batch, nt, nip, Cw)
+    kw = dict(ln_gamma=ctx.f(Cw, scale=0.2, shift=1.0), ln_beta=ctx.f(Cw, scale=0.2)) if ln else {}
+    vn = ctx.out_flat(batch, heads, nip) if vnorm else None
+    fu = ctx.put(torch.tensor(fusion, dtype=F32)) if fusion else None
+    ctx.rec.cross_attention_lnq(hs, ctx.w(Cw, Cw), kt, vt, kip, vip, batch=batch, heads=heads, nq=nq, nt=nt, nip=nip, d=d, vnorm=vn, fusion=fu,
+                                out=ctx.out(batch * nq, Cw), **kw)
+
+
+add("lnq-d160-nip0-nt80-ln", lambda c: _lnq(c, 1, 8, 160, 200, 80, 0, ln=True))
+add("lnq-d160-nip16-nt1", lambda c: _lnq(c, 2, 2, 160, 200, 1, 16, ln=False, vnorm=True))
+add("lnq-d160-nip1-nt80-ln-fusion", lambda c: _lnq(c, 1, 2, 160, 200, 80, 1, ln=True, fusion=(2.0, 0.0)))
+add("lnq-d80-nip1-nt80-ln", lambda c: _lnq(c, 1, 8, 80, 200, 80, 1, ln=True, vnorm=True))
+add("lnq-d80-nip16-nt1-ln-fusion", lambda c: _lnq(c, 2, 4, 80, 200, 1, 16, ln=True, fusion=(0.0, 2.0)))
+add("lnq-d80-nip0-nt80", lambda c: _lnq(c, 1, 4, 80, 200, 80, 0, ln=False))
+
+
+def _fused(ctx, Cw, batch, nt, nip, *, ln, rows=0, fusion=None, vnorm=True):
+    heads, d, nq = 8, Cw // 8, 128
+    rec = ctx.rec
+    kt, vt, kip, vip = _kv(ctx, batch, nt, nip, Cw)
+    vn = ctx.out_flat(batch, heads, nip) if vnorm else None
+    kimg, vimg = rec.xattn_pack_kv(kt, vt, kip, vip, batch=batch, heads=heads, d=d, nt=nt, nip=nip, vnorm=vn)
+    hs = ctx.put((ctx.randn(batch * nq, Cw) * 1.5 + 0.5).to(F16), Cw + 8)
+    kw = dict(ln_gamma=ctx.f(Cw, scale=0.2, shift=1.0), ln_beta=ctx.f(Cw, scale=0.2)) if ln else {}
+    fu = ctx.put(torch.tensor(fusion, dtype=F32)) if fusion else None
+    # wo: the packed matrix itself is drawn (the reference unpacks it with pv_xattn_fused_wo_slot)
+    _, p = rec.cross_attention_fused(hs, ctx.w(Cw, Cw), ctx.w(Cw, Cw), ctx.f(Cw), kimg, vimg, batch=batch, nq=nq, heads=heads, d=d, nt=nt, nip=nip, fusion=fu,
+                                     out=ctx.out(batch * nq, Cw), **kw)
+    p.rows_per_workgroup = rows
+
+
+add("fused-c320-b1-nt65-nip1-ln", lambda c: _fused(c, 320, 1, 65, 1, ln=True))
+add("fused-c320-b3-nt77-nip2", lambda c: _fused(c, 320, 3, 77, 2, ln=False, fusion=(2.0, 0.0)))
+add("fused-c320-b1-nt80-nip16-ln", lambda c: _fused(c, 320, 1, 80, 16, ln=True, fusion=(1.0, 1.0), vnorm=False))
+add("fused-c640-b1-nt65-nip16-ln-rows64", lambda c: _fused(c, 640, 1, 65, 16, ln=True, rows=64))
+add("fused-c640-b3-nt80-nip1-rows128", lambda c: _fused(c, 640, 3, 80, 1, ln=False, rows=128, fusion=(0.0, 2.0)))
+add("fused-c640-b1-nt77-nip2-ln-rows128", lambda c: _fused(c, 640, 1, 77, 2, ln=True, rows=128, vnorm=False))
+add("fused-c640-b3-nt77-nip1-ln", lambda c: _fused(c, 640, 3, 77, 1, ln=True))
+
+
+# ============================================================================================================================== pv_row_gemm
+def _row_gemm(ctx, M, N, *, ln, geglu, bias, x_norm_rpi=0, const_row=False):
+    x = ctx.randn(M, 320) * 1.5 + 0.5
+    if const_row:
+        x[M // 2] = 0.3                                      # zero variance (0.3 is no dyadic number: its fp32 sums round): the normalised row is 0, the result the folded bias
+    kw = {}
+    if ln:
+        kw.update(ln_gamma=ctx.f(320, scale=0.2, shift=1.0), ln_beta=ctx.f(320, scale=0.2))
+    if x_norm_rpi:
+        tab = torch.stack([1.0 + 0.2 * ctx.randn(M // x_norm_rpi, 320), 0.3 * ctx.randn(M // x_norm_rpi, 320)], 1)
+        kw.update(x_norm=ctx.put(tab.contiguous()), rows_per_image=x_norm_rpi)
+    ctx.rec.row_gemm(ctx.put(x.to(F16), 328), ctx.w(N, 320), bias=ctx.f(N) if bias else None, geglu=geglu, out=ctx.out(M, N // 2 if geglu else N), **kw)
+
+
+add("rowgemm-m1-ln-bias", lambda c: _row_gemm(c, 1, 320, ln=True, geglu=False, bias=True))
+add("rowgemm-m257-ln-geglu", lambda c: _row_gemm(c, 257, 640, ln=True, geglu=True, bias=False))
+add("rowgemm-m257-plain", lambda c: _row_gemm(c, 257, 960, ln=False, geglu=False, bias=False))
+add("rowgemm-m1-geglu-bias", lambda c: _row_gemm(c, 1, 640, ln=False, geglu=True, bias=True))
+add("rowgemm-m257-ln-geglu-bias", lambda c: _row_gemm(c, 257, 640, ln=True, geglu=True, bias=True))
+add("rowgemm-m256-groupnorm-table-two-images", lambda c: _row_gemm(c, 256, 320, ln=False, geglu=False, bias=True, x_norm_rpi=128))
+add("rowgemm-m257-ln-constant-row", lambda c: _row_gemm(c, 257, 320, ln=True, geglu=False, bias=True, const_row=True))
+
+
+# ============================================================================================================================== norms
+def _layernorm(ctx, rows, cols, *, act=0, const_row=False, zero=False):
+    x = ctx.randn(rows, cols) * 1.5 + 0.5
+    if const_row:
+        x[rows // 2] = -2.3                                  # zero variance, sums that round: y = beta
+    if zero:
+        x.zero_()
+    ctx.rec.layernorm(ctx.put(x.to(F16), cols + 8), ctx.f(cols, scale=0.2, shift=1.0), ctx.f(cols, scale=0.2), act=act, out=ctx.out(rows, cols, gap=16))
+
+
+for _cols in (8, 320, 4096):
+    for _rows in (1, 77):
+        add(f"layernorm-{_rows}x{_cols}", lambda c, r=_rows, k=_cols: _layernorm(c, r, k, act=3 if k == 8 else 0))
+add("layernorm-constant-row-77x320", lambda c: _layernorm(c, 77, 320, const_row=True))
+add("layernorm-constant-row-77x640", lambda c: _layernorm(c, 77, 640, const_row=True))
+add("layernorm-all-zero-5x320", lambda c: _layernorm(c, 5, 320, zero=True))
+
+
+def _groupnorm(ctx, batch, hw, c0, c1=0, *, act=0, from_colstats=False, const_group=False):
+    x0 = ctx.randn(batch * hw, c0) * 1.5 + 0.5
+    if const_group:
+        x0[:hw, : c0 // 32] = 1.3                            # group 0 of image 0: zero variance, sums that round: y = beta
+    gap = 0 if from_colstats else 8
+    x0 = ctx.put(x0.to(F16), c0 + gap)
+    x1 = ctx.put(ctx.randn(batch * hw, c1).to(F16), c1 + gap) if c1 else None
+    if from_colstats:
+        ctx.colstats_for(x0)
+        if c1:
+            ctx.colstats_for(x1)
+    ctx.rec.groupnorm(x0, ctx.f(c0 + c1, scale=0.2, shift=1.0), ctx.f(c0 + c1, scale=0.2), batch=batch, hw=hw, x1=x1, act=act)
+
+
+add("groupnorm-hw1-c64", lambda c: _groupnorm(c, 3, 1, 64))
+add("groupnorm-hw25-c2560-silu", lambda c: _groupnorm(c, 3, 25, 2560, act=1))
+add("groupnorm-hw25-c64-dual", lambda c: _groupnorm(c, 3, 25, 32, 32))
+add("groupnorm-hw64-c2560-dual", lambda c: _groupnorm(c, 3, 64, 1280, 1280, act=1))
+add("groupnorm-hw64-c64-from-colstats", lambda c: _groupnorm(c, 3, 64, 64, from_colstats=True))
+add("groupnorm-hw64-c2560-dual-from-colstats", lambda c: _groupnorm(c, 3, 64, 1280, 1280, from_colstats=True, act=1))
+add("groupnorm-hw25-c64-constant-group", lambda c: _groupnorm(c, 3, 25, 64, const_group=True))
+add("groupnorm-hw64-c64-constant-group-from-colstats", lambda c: _groupnorm(c, 3, 64, 64, const_group=True, from_colstats=True))
+
+
+# ============================================================================================================================== small launchers
+def _conv_out(c, cout):
+    c.rec.conv_out(c.put(c.randn(2 * 5 * 7, 64).to(F16)), c.w(cout, 9 * 64), c.f(cout), batch=2, cin=64, h=5, wd=7, cout=cout, out=c.out_flat(2, cout, 5, 7))
+
+
+add("conv-out-5x7-cout4", lambda c: _conv_out(c, 4))
+add("conv-out-5x7-cout3", lambda c: _conv_out(c, 3))
+
+
+def _state(c, idx, rows):
+    return c.put(torch.tensor([idx, rows], dtype=I32))
+
+
+def _timestep(c):
+    c.rec.timestep_embedding(c.put(torch.tensor([999.0, 500.5, 1.0])), None, 3, 320)
+    table = [981.0, 961.0, 941.0, 921.0, 901.0, 881.0, 861.0, 1.0]
+    c.rec.timestep_embedding(c.put(torch.tensor(table)), _state(c, 3, 8), 1, 1280)
+    c.rec.timestep_embedding(c.put(torch.tensor(table)), _state(c, 19, 8), 3, 6)       # a step past the table reads its last row
+
+
+add("timestep-embedding-rows3", _timestep)
+
+
+def _cfg(c, masked):
+    B, ch, h, w = 2, 4, (6 if masked else 5), (6 if masked else 7)          # the masked form needs hw % 4 == 0
+    steps = 5
+    coef = c.put(torch.cat([c.randn(steps, 7, scale=0.5) + torch.tensor([1.0, -0.5, 0.8, 0.6, -0.3, 0.9, 0.4]), torch.zeros(steps, 1)], 1).contiguous())
+    for idx in (0, 1, steps - 1):
+        t = [c.f(B, ch, h, w) for _ in range(4)]
+        if masked:
+            m = torch.rand(B, 1, h, w, generator=c.g)
+            m[0, 0, :2] = 1.0
+            m[0, 0, 2:4] = 0.0
+            c.rec.cfg_dpm_step_masked(*t, coef, _state(c, idx, steps), 7.5, c.put(m), c.f(B, ch, h, w), c.f(B, ch, h, w))
+        else:
+            c.rec.cfg_dpm_step(*t, coef, _state(c, idx, steps), 7.5)
+
+
+add("cfg-dpm-step-5x7-steps-0-1-last", lambda c: _cfg(c, False))
+add("cfg-dpm-step-masked-6x6-steps-0-1-last", lambda c: _cfg(c, True))
+add("pointwise-nchw-5x7", lambda c: c.rec.pointwise_nchw(c.f(2, 4, 35), c.f(4, 4), c.f(4), batch=2, cin=4, cout=4, hw=35))
+add("posterior-sample-5x7", lambda c: c.rec.posterior_sample(c.f(2, 8, 5, 7, scale=3.0), c.f(2, 4, 5, 7), out=c.out_flat(2 * 4 * 5 * 7).view(2, 4, 5, 7)))
+add("im2col-5x7-kpad64", lambda c: c.rec.im2col3x3(c.f(2, 4, 5, 7), batch=2, cin=4, h=5, wd=7, kpad=64))
+# pv_softmax_rows takes cols % 8 == 0 only (header): the ragged extents are the row counts 77 / 257 and the first valid widths above them
+add("softmax-rows-77x80", lambda c: c.rec.softmax_rows(c.h(77, 80, scale=3.0), scale=0.3))
+add("softmax-rows-257x264", lambda c: c.rec.softmax_rows(c.h(257, 264, scale=3.0), scale=0.05))
+
+
+# ============================================================================================================================== value edges
+def _cancelling(c):
+    """[x | x] . [w | -w]^T: every product has its negative in the sum, the exact result is the bias."""
+    x = c.randn(130, 64).to(F16)
+    w = c.randn(160, 64, scale=0.125).to(F16)
+    _linear(c, 130, 160, 128, a=(c.put(x, 72), c.put(x.clone(), 80)), wt=c.put(torch.cat([w, -w], 1).contiguous()), bias=True)
+
+
+def _zero_gemm(c):
+    _linear(c, 130, 160, 64, a=(c.put(torch.zeros(130, 64, dtype=F16), 72), None), bias=True, act=1)
+    _conv(c, 2, 5, 7, 64, 128, a=(c.put(torch.zeros(70, 64, dtype=F16), 72), None), bias=False)
+
+
+add("gemm-cancelling-operands", _cancelling)
+add("gemm-all-zero-input", _zero_gemm)
+
+
+#: Instantiations no argument and no per-call switch can select: the only symbols the dispatch sweep may leave unaudited
+EXEMPT = {
+    "big_tile_kernel<false, false, 4, 1, false>": "the 128-row form of the 256 x 320 tile: behind PV_GEMM_BIG128, read once per process",
+    "big_tile_kernel<true, false, 4, 1, false>": "the same with column statistics: behind PV_GEMM_BIG128, read once per process",
+    "attn_kernel<40, 4, false>": "d = 40 without the LDS-DMA ring: needs PV_ATTN_NO_DMA (read once per process) or a K / V operand of 2 GiB or more",
+    "attn_kernel<40, 2, false>": "d = 40 without the LDS-DMA ring: needs PV_ATTN_NO_DMA (read once per process) or a K / V operand of 2 GiB or more",
+    **{f"attn8_kernel<{v}>": "a non-default form of the 8-wave kernel: PV_ATTN8 selects it, kept for the measurements of EXPERIMENTS.md"
+       for v in (0, 1, 9, 13, 33, 49, 73, 201, 225, 241, 481)},
+}
+#: switches read once per process that change which kernel (or workgroup shape) a launch takes; the suite runs with none of them set
+PROCESS_SWITCHES = ("PV_GEMM_BIG128", "PV_XF_ROWS", "PV_ATTN_NO_DMA", "PV_ATTN_NQ", "PV_GEMM_MI2", "PV_GEMM_TPW")
+
+
+# ============================================================================================================================== dispatch sweep
+SWEEP_M = (1, 65, 130, 257, 4096, 65536, 131073)
+SWEEP_BIG_MIN = (0, 1, 128, -1)
+
+
+def _sweep_gemm(sym: set):
+    probe = gemm_symbol
+    for big in SWEEP_BIG_MIN:
+        for M in SWEEP_M:
+            for N in (128, 160, 256, 320, 640, 1024, 1280):
+                for K in (64, 192, 320, 640, 1280):
+                    for c1 in (0, K):
+                        base = _lin_fields(M, N, K, big_tile_min=big, c1=c1, lda1=c1, a1=0x1000 if c1 else 0, hout=100)
+                        for extra in ({}, dict(out_f32=1), dict(colstats=0x1000), dict(geglu=1, ldc=N // 2), dict(ln_rowsum=0x1000), dict(geglu=1, ldc=N // 2, ln_rowsum=0x1000),
+                                      dict(residual=0x1000, ldr=N, bias=0x1000, act=1, rowadd=0x1000, rowadd_ld=N)):
+                            for sk in (0, 2, 3):
+                                sym.add(probe(**{**base, **extra}, splitk=sk, splitk_ws=0x1000 if sk else 0))
+        geos = [(2, 5, 7), (1, 10, 10), (1, 5, 5), (1, 4, 64), (2, 4, 64), (1, 8, 32), (2, 8, 32), (16, 64, 64), (16, 32, 32), (16, 16, 16), (4, 96, 96), (4, 24, 24)]
+        for patch in (None, "0", "1"):
+            with environment({} if patch is None else {"PV_CONV_PATCH": patch}, folds=False):
+                for b, h, w in geos:
+                    for stride, up, pad in ((1, 0, 1), (2, 0, 1), (2, 0, 0), (1, 1, 1)):
+                        hl, wl = (2 * h, 2 * w) if up else (h, w)
+                        ho, wo = ((hl + (2 if pad else 1) - 3) // 2 + 1, (wl + (2 if pad else 1) - 3) // 2 + 1) if stride == 2 else (hl, wl)
+                        for cin, c1 in ((64, 0), (64, 64), (128, 0), (320, 0), (640, 640)):
+                            for N in (128, 160, 320, 640):
+                                base = dict(c0=cin, c1=c1, lda0=cin, lda1=c1, a1=0x1000 if c1 else 0, N=N, ldc=N, M=b * ho * wo, taps=9, batch=b, hin=h, win=w, hout=ho, wout=wo,
+                                            stride=stride, upsample=up, pad=pad, big_tile_min=big)
+                                for extra in ({}, dict(colstats=0x1000), dict(a_norm=0x1000, a_norm_act=1), dict(a_norm=0x1000, colstats=0x1000), dict(out_f32=1)):
+                                    for sk in (0, 2, 3, 5, 8):
+                                        sym.add(probe(**{**base, **extra}, splitk=sk, splitk_ws=0x1000 if sk else 0))
+
+
+def _sweep_attention(sym: set):
+    for env in ({}, {"PV_ATTN8_MIN": "1"}, {"PV_ATTN8": "-1"}, {"PV_ATTN8": "-1", "PV_ATTN8_MIN": "1"}):
+        with environment(env, folds=False):
+            for d in (40, 64, 80, 160):
+                for batch, heads in ((1, 2), (2, 8), (16, 8), (64, 8), (128, 8)):
+                    for nq in (1, 65, 257, 600, 1024, 4096, 9216):
+                        for nk in {1, 77, nq}:
+                            for causal in (0, 1):
+                                ld = 3 * heads * d + 8
+                                sym.add(attn_symbol(batch=batch, heads=heads, nq=nq, nk=nk, d=d, causal=causal, ldq=ld, ldk=ld, ldv=ld, ldo=heads * d, lse=0))
+
+
+DISPATCHED = ("gemm_conv_kernel<", "big_tile_kernel<", "attn_kernel<", "attn8_kernel<")
+_SWEPT: Optional[frozenset] = None
+
+
+def swept_symbols() -> frozenset:
+    """Every kernel symbol ``pv_gemm_conv_kernel_info`` / ``pv_attention_kernel_info`` name over a grid of contract-valid parameter blocks (M, every N /
+    K family, taps, stride, upsample, split-K, big_tile_min, the per-call switches) - no GPU needed.  Blocks the library rejects count for nothing."""
+    global _SWEPT
+    if _SWEPT is None:
+        sym: set = set()
+        _sweep_gemm(sym)
+        _sweep_attention(sym)
+        sym.discard("")
+        _SWEPT = frozenset(sym)
+    return _SWEPT
+
+
+def by_name(name: str) -> Case:
+    return next(c for c in CASES if c.name == name)

@@ -227,17 +227,18 @@ class Auditor:
             v[k], base[k] = make_view(pool, addr, buf, f"{where}, field {k}")
 
         # fields whose extent depends on device state (the step index) are resolved after the state
-        if name in ("pv_timestep_embedding", "pv_cfg_dpm_step") and L.get("state") is not None:
+        cfg = name in ("pv_cfg_dpm_step", "pv_cfg_dpm_step_masked")
+        if (name == "pv_timestep_embedding" or cfg) and L.get("state") is not None:
             resolve("state", L["state"])
             idx = A.step_index(v["state"]) if "state" in v else 0
             if name == "pv_timestep_embedding":
                 L["timesteps"] = A.Buf(A.F32, 1, idx + 1, 0)
-            if name == "pv_cfg_dpm_step":
+            if cfg:
                 L["coef"] = A.Buf(A.F32, 1, (idx + 1) * 8, 0)
         for k, buf in L.items():
             if k not in v and buf is not None:
                 resolve(k, buf)
-        if name == "pv_cfg_dpm_step":
+        if cfg:
             v["coef"] = v["coef"][:, A.step_index(v["state"]) * 8:][:, :8]
         if name == "pv_cross_attention_fused" and p.kimg not in self.kv:
             raise AuditError(f"{where}: kimg {p.kimg:#x} was not built by an audited pv_xattn_pack_kv")

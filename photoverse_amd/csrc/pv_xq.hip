@@ -381,7 +381,7 @@ extern "C" int pv_cross_attention_lnq(const pv_xattn_lnq_params* p, void* stream
         (p->ldkt % 4) || (p->ldvt % 8) || (p->nip > 0 && ((p->ldkip % 4) || (p->ldvip % 8))))
         return (int)hipErrorInvalidValue;
     const size_t C = (size_t)p->heads * p->d;
-    if (C % D) return (int)hipErrorInvalidValue;
+    if ((C % D) || (C % 64)) return (int)hipErrorInvalidValue;       // whole 160-feature blocks, and the GEMM walks K = C in 64-deep stages (nk = C / 64)
     if (C * C * 2 >= (1ull << 31)) return (int)hipErrorInvalidValue;
     // the kernel addresses rows through 32-bit buffer offsets (0x80000000 is its out-of-range sentinel): every extent must stay below 2 GiB
     const size_t rows_m1 = (size_t)p->batch * p->nq - 1;

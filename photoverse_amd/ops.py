@@ -580,8 +580,8 @@ class Recorder:
 
     @staticmethod
     def xattn_lnq_supported(C: int, heads: int, nt: int, nip: int) -> bool:
-        """d = 160 (C = 1280: one head per 160-feature block) or d = 80 (C = 640: two heads per block)."""
-        return Recorder.XLNQ and C % heads == 0 and C // heads in (160, 80) and 0 < nt <= 80 and 0 <= nip <= 16
+        """d = 160 (C = 1280: one head per 160-feature block) or d = 80 (C = 640: two heads per block); C a multiple of 320 (the launcher rejects the rest)."""
+        return Recorder.XLNQ and C % heads == 0 and C // heads in (160, 80) and C % 320 == 0 and 0 < nt <= 80 and 0 <= nip <= 16
 
     def cross_attention_lnq(self, hs, wq, kt, vt, kip, vip, *, batch, heads, nq, nt, nip, d=None, ln_gamma=None, ln_beta=None, ln_eps=1e-5,
                             w_text=1.0, w_ip=1.0, vnorm=None, fusion=None, out=None):

@@ -272,6 +272,37 @@ def test_pointwise_softmax_posterior_references():
     close(got, (mm[:, 0] + torch.exp(0.5 * mm[:, 1].clamp(-30, 20)) * e.double().reshape(2, 4)).reshape(1, -1))
 
 
+def test_masked_cfg_step_is_the_cfg_step_followed_by_the_blend():
+    """pv_cfg_dpm_step_masked against an independent formulation: ``ref_cfg`` on the same arguments, then the inpainting blend in plain torch."""
+    g = torch.Generator().manual_seed(15)
+    B, ch, hw, steps = 2, 4, 12, 3
+    n = B * ch * hw
+    t = {k: torch.randn(1, n, generator=g) for k in ("eps_uncond", "eps_cond", "latents", "x0_prev", "known", "noise")}
+    coef = torch.randn(steps, 8, generator=g)
+    mask = torch.rand(B, hw, generator=g)
+    mask[0, :4], mask[0, 4:8] = 1.0, 0.0
+    state = torch.tensor([[1, steps]], dtype=torch.int32)
+    a = SimpleNamespace(guidance=7.5, n=n, channels=ch, hw=hw)
+    v = dict(t, coef=coef[1:2], state=state, mask=mask)
+    L = A.layout_cfg_masked(a)
+    assert (L["mask"].rows, L["mask"].cols) == (B, hw) and L["known"].cols == n and L["latents"].role == "inout" and L["known"].role == "in"
+    base = A.ref_cfg(a, {k: v[k] for k in ("eps_uncond", "eps_cond", "latents", "x0_prev", "coef", "state")})
+    got = A.ref_cfg_masked(a, v)
+    assert torch.equal(got["x0_prev"].ref, base["x0_prev"].ref)                       # x0_prev receives the unblended x0
+    m = mask.double()[:, None, :].expand(B, ch, hw).reshape(1, n)
+    k = coef[1, 5].double() * t["known"].double() + coef[1, 6].double() * t["noise"].double()
+    close(got["latents"].ref, m * base["latents"].ref + (1 - m) * k, 1e-14)
+    keep, gen = (m == 0)[0], (m == 1)[0]
+    assert keep.sum() == ch * 4 and gen.sum() == ch * 4
+    assert torch.equal(got["latents"].ref[0, keep], k[0, keep]) and torch.equal(got["latents"].ref[0, gen], base["latents"].ref[0, gen])
+    # m == 1 adds only the blend's own roundings to pv_cfg_dpm_step's bound; m == 0 leaves k's: a handful of fp32 ulps either way
+    assert (got["latents"].bound[0, gen] <= base["latents"].bound[0, gen] + 4 * A.U32 * base["latents"].ref[0, gen].abs() + 1e-30).all()
+    assert (got["latents"].bound[0, keep] <= 6 * A.U32 * (coef[1, 5].abs() * t["known"].abs() + coef[1, 6].abs() * t["noise"].abs())[0, keep].double() + 1e-30).all()
+    # the comparator rejects a blend with the mask inverted
+    assert PA.compare(got, {"latents": ((1 - m) * base["latents"].ref + m * k).float(), "x0_prev": base["x0_prev"].ref.float()})[0]
+    assert not PA.compare(got, {"latents": got["latents"].ref.float(), "x0_prev": base["x0_prev"].ref.float()})[0]
+
+
 # ------------------------------------------------------------------------------------------------------------------ comparator
 def _gemm_expect(seed=11, M=200, K=512, N=128, store_rel=None):
     g = torch.Generator().manual_seed(seed)
@@ -374,7 +405,7 @@ def test_every_recorded_launcher_has_a_reference():
     for name in ("pv_gemm_conv", "pv_attention", "pv_cross_attention", "pv_cross_attention_fused", "pv_cross_attention_lnq", "pv_xattn_pack_kv",
                  "pv_row_gemm", "pv_layernorm", "pv_groupnorm_stats", "pv_groupnorm_stats_from_colstats", "pv_groupnorm_scale_shift",
                  "pv_groupnorm_apply", "pv_im2col3x3", "pv_conv_out", "pv_timestep_embedding", "pv_cfg_dpm_step", "pv_step_advance",
-                 "pv_pointwise_nchw", "pv_softmax_rows", "pv_posterior_sample"):
+                 "pv_pointwise_nchw", "pv_softmax_rows", "pv_posterior_sample", "pv_cfg_dpm_step_masked"):
         assert name in A.REF, name
 
 

@@ -1,0 +1,55 @@
+"""Every case of the edge-case catalogue (``oracle.edge_cases``) through ``oracle.plan_audit.Auditor``: each kernel ``pv_gemm_conv`` / ``pv_attention`` can
+dispatch to, and every other inference launcher, at its smallest ragged shape, with all the Auditor's checks unchanged - fp64 reference from the
+launch's own parameter block, ``oracle.abi_ref``'s derived element and aggregate bounds (no tolerance of this file's own), outputs poisoned with NaN,
+every byte of the output storages outside the described extents, a bit-identical second run - on guarded tensors: outputs sit inside a patterned arena a
+stray tile cannot leave, inputs inside NaN, so a read outside an input's extent that reaches a result fails the finite check.
+
+Wall time of this file alone on one MI355X: 7.3 s for its 127 tests (5.3 s of it in the audits, 177 launches); the rest of the GPU suite on the same box,
+same visit: 181.0 s for 314 tests (EXPERIMENTS.md, "Edge audit")."""
+import time
+
+import pytest
+import torch
+
+from oracle import edge_cases as E
+from oracle.plan_audit import AuditError, Auditor
+
+pytestmark = pytest.mark.gpu
+
+T0 = time.time()
+
+
+@pytest.fixture(scope="module")
+def auditor():
+    from photoverse_amd import _lib
+    aud = Auditor(_lib.load())
+    yield aud
+    print("\nedge audit coverage (worst element error / bound, worst rel-L2 / aggregate bound):\n" + aud.table())
+    print(f"edge audit: {aud.audited} launches of {len(E.CASES)} cases in {time.time() - T0:.1f} s")
+
+
+@pytest.mark.parametrize("name", [c.name for c in E.CASES])
+def test_edge_case(name, auditor):
+    c = E.by_name(name)
+    try:
+        with E.environment(c.env):              # the per-call switches hold while the case is recorded and while its launches run
+            rec = E.build(c, "cuda")
+            assert not E.unguarded(rec)
+            tags = [t[0] for t in rec.tags]
+            for want in c.expect:
+                assert want in tags, (want, tags)
+            n = auditor.audit(name, rec)
+    except AssertionError:
+        raise
+    except Exception as e:                      # a HIP error: nothing more is started on a device that has faulted
+        pytest.exit(f"{name}: {type(e).__name__}: {e}", returncode=3)
+    assert n == len(rec.calls) and n > 0
+    del rec
+    torch.cuda.empty_cache()
+
+
+def test_every_dispatchable_kernel_was_audited(auditor):
+    """The kernel symbols audited above are exactly the ones the dispatch sweep of tests/test_edge_audit_cpu.py requires."""
+    audited = {k[2] for k in auditor.rows if k[2].startswith(E.DISPATCHED)}
+    required = set(E.swept_symbols()) - set(E.EXEMPT)
+    assert audited == required, (sorted(required - audited), sorted(audited - required))
