@@ -6,7 +6,9 @@ the offline environment: ``--model_path random`` (seeded random-init weights), `
 files needed), ``--seed``, ``--latent_size``.  Images are written as PNG like the reference (``generate.py:86-90``).
 
 Beyond the reference: ``--mask_image_path`` (inpainting: white = regenerate) with ``--target_image_path`` (the photograph to edit; the identity
-still comes from ``--input_image_path``), ``--strength`` (img2img: run only the last part of the schedule) and ``--no_paste_back``.
+still comes from ``--input_image_path``), ``--strength`` (img2img: run only the last part of the schedule) and ``--no_paste_back``;
+``--hires_latent_size`` (two-pass high-resolution generation: generate at ``--latent_size``, upscale the latents, re-noise them and run the last
+``--hires_strength`` of a ``--hires_timesteps`` schedule at the large size; the images are ``8 * hires_latent_size`` pixels).
 """
 import argparse
 import os
@@ -41,6 +43,10 @@ parser.add_argument("--target_image_path", type=str, default=None, help="The pho
 parser.add_argument("--strength", type=float, default=1.0,
                     help="Fraction of the schedule to run, starting from the noised image (with --from_noised_image or --mask_image_path)")
 parser.add_argument("--no_paste_back", action="store_true", help="Return the decoded image as it is instead of the target's own pixels outside the mask")
+parser.add_argument("--hires_latent_size", type=int, default=None,
+                    help="Second pass at this latent size (>= --latent_size): upscale the first pass's latents, re-noise and refine them")
+parser.add_argument("--hires_strength", type=float, default=0.5, help="Fraction of the second pass's schedule to run (with --hires_latent_size)")
+parser.add_argument("--hires_timesteps", type=int, default=None, help="Steps of the second pass's schedule (default: --num_timesteps)")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -110,7 +116,8 @@ if __name__ == "__main__":
         out = run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler, device,
                             args.encoder_layers_idx, latent_size=args.latent_size, guidance_scale=args.guidance_scale,
                             timesteps=args.num_timesteps, from_noised_image=args.from_noised_image, seed=args.seed,
-                            strength=args.strength, inpaint_mask=prepare_mask(args), paste_back=not args.no_paste_back)
+                            strength=args.strength, inpaint_mask=prepare_mask(args), paste_back=not args.no_paste_back,
+                            hires_latent_size=args.hires_latent_size, hires_strength=args.hires_strength, hires_timesteps=args.hires_timesteps)
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

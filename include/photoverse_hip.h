@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PV_ABI_VERSION 18
+#define PV_ABI_VERSION 19
 
 enum pv_act { PV_ACT_NONE = 0, PV_ACT_SILU = 1, PV_ACT_QUICK_GELU = 2, PV_ACT_LEAKY_RELU = 3, PV_ACT_GELU = 4 };
 
@@ -522,6 +522,15 @@ int pv_composite_clamp_f32(const float* gen, const float* orig, const float* mas
  * cb = sqrt(1 - acp[t_b])) and the 1/scaling_factor latent scaling (infer.py:121) */
 int pv_affine_rows_f32(const float* x, const float* y, const float* ca, const float* cb, float* out, int64_t per_sample,
                        int32_t batch, void* stream);
+/* (ABI 19) out[b][c] = ca[b] * bilinear(x[b][c]: h x w -> oh x ow) (+ cb[b] * y[b][c])   fp32 NCHW, contiguous
+ * bilinear = F.interpolate(mode="bilinear", align_corners=False, antialias=False):
+ *   src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1), weight = src - i0, per axis
+ * ca NULL = 1; y and cb are given together or both NULL; x, y, ca, cb are read only; out must not overlap x.
+ * Any h, w, oh, ow >= 1; every operand below 2 GiB.  At oh == h, ow == w without ca / y / cb the result is x bit for bit (the weights are exactly 0).
+ * Nothing in the reference: the step between the two passes of a high-resolution generation ([EXT] the "hires fix" of A1111 / diffusers' latent
+ * upscale), x_start = sqrt(acp[t]) * upsample(latents) + sqrt(1 - acp[t]) * noise, in one launch. */
+int pv_resize_bilinear_affine_f32(const float* x, const float* y, const float* ca, const float* cb, float* out,
+                                  int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t oh, int32_t ow, void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

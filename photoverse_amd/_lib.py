@@ -161,6 +161,7 @@ SIGNATURES = {
     "pv_softmax_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "pv_pointwise_nchw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "pv_affine_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "pv_resize_bilinear_affine_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "pv_posterior_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "pv_reduce_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "pv_clamp_f32": (c_int, [c_void_p, c_float, c_float, c_int64, c_void_p]),
@@ -184,7 +185,7 @@ def kernel_info(fn, params):
         raise ValueError(f"{fn.__name__ if hasattr(fn, '__name__') else 'kernel_info'}: the library rejects this parameter block (hipError {rc})")
     return buf.value.decode(), int(wgs.value)
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _lib = None
 
 

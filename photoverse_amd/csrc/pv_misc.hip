@@ -466,6 +466,55 @@ __global__ void affine_rows_kernel(const float* x, const float* y, const float* 
     if (y) v += cb[b] * y[i];
     out[i] = v;
 }
+// one axis of F.interpolate(mode="bilinear", align_corners=False): src = max((dst + 0.5) * in / out - 0.5, 0) = max(((2 dst + 1) in - out) / (2 out), 0).
+// The numerator is an exact integer in fp64 (in, out < 2^29), so the only rounding is the division's: at in == out it is dst itself and the weight exactly 0.
+__device__ __forceinline__ void bilinear_taps(int dst, int in, int out, int& i0, int& i1, float& wt) {
+    const double src = fmax(((2.0 * dst + 1.0) * in - out) / (2.0 * out), 0.0);
+    i0 = min((int)src, in - 1);
+    i1 = min(i0 + 1, in - 1);
+    wt = (float)(src - (double)i0);
+}
+// weight 0 returns a itself (also when b is not finite, and with the sign of a zero)
+__device__ __forceinline__ float bilinear_mix(float a, float b, float wt) { return wt == 0.f ? a : (1.f - wt) * a + wt * b; }
+
+// out[b][c] = ca[b] * bilinear(x[b][c]: h x w -> oh x ow) (+ cb[b] * y[b][c]) over NCHW fp32; ca NULL = 1.  V outputs of one row per thread:
+// V = 4 (ow % 4 == 0, y / out 16-byte aligned) reads y and writes out as float4; V = 1 takes every other shape.  x is gathered: 4 taps per output.
+template <int V>
+__global__ void resize_bilinear_affine_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ ca,
+                                              const float* __restrict__ cb, float* __restrict__ out, int channels, int h, int w, int oh, int ow, int n) {
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (i >= n) return;
+    const int row = i / ow, ox = i - row * ow;          // V divides ow: the V outputs share the row
+    const int plane = row / oh, oy = row - plane * oh;
+    const int b = plane / channels;
+    int y0, y1;
+    float wy;
+    bilinear_taps(oy, h, oh, y0, y1, wy);
+    const float* r0 = x + ((long)plane * h + y0) * w;
+    const float* r1 = x + ((long)plane * h + y1) * w;
+    const float a = ca ? ca[b] : 1.f;
+    float v[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        int x0, x1;
+        float wx;
+        bilinear_taps(ox + j, w, ow, x0, x1, wx);
+        const float r = bilinear_mix(bilinear_mix(r0[x0], r0[x1], wx), bilinear_mix(r1[x0], r1[x1], wx), wy);
+        v[j] = ca ? a * r : r;
+    }
+    if constexpr (V == 4) {
+        float4_t o = {v[0], v[1], v[2], v[3]};
+        if (y) {
+            const float4_t yv = *reinterpret_cast<const float4_t*>(y + i);
+            const float c = cb[b];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] += c * yv[j];
+        }
+        *reinterpret_cast<float4_t*>(out + i) = o;
+    } else {
+        out[i] = y ? v[0] + cb[b] * y[i] : v[0];
+    }
+}
 // posterior sample of the VAE encoder: out = mean + exp(0.5 * clamp(logvar, -30, 20)) * eps; moments = [B][2c][hw] (mean | logvar)
 __global__ void posterior_sample_kernel(const float* moments, const float* eps, float* out, long chw, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -506,6 +555,24 @@ extern "C" int pv_affine_rows_f32(const float* x, const float* y, const float* c
     if (!x || !ca || !out || per_sample <= 0 || batch <= 0 || (y && !cb)) return (int)hipErrorInvalidValue;
     const long n = (long)per_sample * batch;
     hipLaunchKernelGGL(affine_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, ca, cb, out, (long)per_sample, n);
+    return PV_CHECK_LAUNCH();
+}
+
+extern "C" int pv_resize_bilinear_affine_f32(const float* x, const float* y, const float* ca, const float* cb, float* out, int32_t batch,
+                                             int32_t channels, int32_t h, int32_t w, int32_t oh, int32_t ow, void* stream) {
+    if (!x || !out || batch <= 0 || channels <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ((y != nullptr) != (cb != nullptr)))
+        return (int)hipErrorInvalidValue;
+    // every operand below 2 GiB = 2^29 floats (so the kernel indexes with int); checked factor by factor, the full product may not fit 64 bits
+    const int64_t lim = (int64_t)1 << 29, planes = (int64_t)batch * channels;
+    if (planes >= lim || planes * h >= lim || planes * h * w >= lim || planes * oh >= lim || planes * oh * ow >= lim) return (int)hipErrorInvalidValue;
+    const int n = (int)(planes * oh * ow);
+    const bool vec = (ow % 4) == 0 && (reinterpret_cast<uintptr_t>(out) % 16) == 0 && (reinterpret_cast<uintptr_t>(y) % 16) == 0;
+    if (vec)
+        hipLaunchKernelGGL(resize_bilinear_affine_kernel<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, ca, cb, out,
+                           channels, h, w, oh, ow, n);
+    else
+        hipLaunchKernelGGL(resize_bilinear_affine_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, ca, cb, out,
+                           channels, h, w, oh, ow, n);
     return PV_CHECK_LAUNCH();
 }
 

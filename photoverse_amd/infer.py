@@ -10,9 +10,14 @@ device generator (``torch.manual_seed(seed)`` seeds it like the reference's, the
 Beyond the reference ([EXT] diffusers' img2img ``strength`` and inpainting with a 4-channel UNet): ``strength`` starts the loop part-way down
 the schedule from the image noised to that step, ``inpaint_mask`` regenerates only the masked region - the blend with the re-noised known
 latents is part of the solver-step launch (``pv_cfg_dpm_step_masked``) - and ``paste_back`` composites the decoded result onto the input pixels.
+
+Also beyond the reference ([EXT] the two-pass "hires fix" of A1111 / diffusers' latent upscale): with ``hires_latent_size`` the image is generated at
+``latent_size`` (SD-v1.5 was trained at 64), its latents are upscaled and re-noised part-way up the schedule - ``hires_start``, one launch of
+``pv_resize_bilinear_affine_f32`` - and only the last ``hires_strength`` of the schedule runs at the large size, on a second cached ``DenoiseLoop``.
 """
 from __future__ import annotations
 
+import numbers
 from collections import OrderedDict
 
 import torch
@@ -33,6 +38,30 @@ def strength_start(timesteps: int, strength: float) -> int:
     if n_run < 1:
         raise ValueError(f"strength {strength} leaves no step of {timesteps} to run")
     return timesteps - n_run
+
+
+def _is_positive_int(v) -> bool:
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 1
+
+
+def hires_start(latents: torch.Tensor, noise: torch.Tensor, scheduler, timesteps: int, strength: float):
+    """The step between the two passes of a high-resolution generation -> ``(x_start, start)``: ``start = strength_start(timesteps, strength)`` and
+    ``x_start = sqrt(acp[t]) * bilinear(latents -> noise's size) + sqrt(1 - acp[t]) * noise`` with ``t = timesteps[start]`` of ``scheduler`` set to
+    ``timesteps`` steps - ``scheduler.add_noise`` of the upscaled latents - in one launch (``pv_resize_bilinear_affine_f32``).  ``latents`` (B, C, h, w) and
+    ``noise`` (B, C, H, W) live on the HIP device; ``DenoiseLoop.reset(x_start, start)`` takes the result."""
+    from .ops import Recorder, require_cuda
+    start = strength_start(timesteps, float(strength))
+    if latents.dim() != 4 or noise.dim() != 4 or tuple(latents.shape[:2]) != tuple(noise.shape[:2]):
+        raise ValueError(f"hires_start: latents {tuple(latents.shape)} and noise {tuple(noise.shape)} are not (B, C, h, w) and (B, C, H, W)")
+    require_cuda(latents, "latents")
+    scheduler.set_timesteps(timesteps)
+    acp = torch.from_numpy(scheduler.alphas_cumprod)[scheduler.timesteps[start:start + 1].long()].to(torch.float64)     # as scheduler.add_noise
+    batch, dev = latents.shape[0], latents.device
+    ca, cb = (c.float().repeat(batch).to(dev) for c in (acp.sqrt(), (1 - acp).sqrt()))
+    rec = Recorder(dev)
+    x_start = rec.resize_bilinear_affine(latents.detach().float().contiguous(), tuple(noise.shape[2:]), ca, noise.detach().to(dev).float().contiguous(), cb)
+    rec.run()
+    return x_start, start
 
 
 def latent_mask(inpaint_mask: torch.Tensor, batch: int, latent_size: int):
@@ -66,7 +95,7 @@ def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, traini
 def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler,
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
-                  inpaint_mask=None, paste_back=True):
+                  inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
     global batch once and hands each rank its slice.
@@ -74,7 +103,32 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     Keyword-only, beyond the reference: ``strength`` in (0, 1] (with ``from_noised_image`` or ``inpaint_mask``): only the last
     ``int(timesteps * strength)`` steps run, from the image noised to the first of them; 1.0 is the reference's ``from_noised_image``.
     ``inpaint_mask`` (B or 1, 1, H, W) in [0, 1] at the resolution of ``example["pixel_values"]``, 1 = regenerate: starts from the noised image
-    and keeps the latents outside the mask on the image's.  ``paste_back``: outside the mask the returned pixels are ``pixel_values`` themselves."""
+    and keeps the latents outside the mask on the image's.  ``paste_back``: outside the mask the returned pixels are ``pixel_values`` themselves.
+
+    ``hires_latent_size`` (>= ``latent_size``; None: one pass, as ever): a second pass at that size.  The first pass runs as above; its latents go through
+    ``hires_start`` with ``hires_strength`` in (0, 1] of a schedule of ``hires_timesteps`` steps (None: ``timesteps``), and the last
+    ``int(hires_timesteps * hires_strength)`` steps run at the large size under the same conditioning; the result is decoded at that size.
+    ``hires_noise`` (B, C, hires_latent_size, hires_latent_size): the noise of the second pass; otherwise it is drawn right after the first one from the
+    same generator (``seed``) or with ``torch.randn``.  Not with ``inpaint_mask`` or ``training_mode``."""
+    hires = hires_latent_size is not None
+    if hires:                                          # before anything else: the first pass must not run for a second one that cannot
+        if not _is_positive_int(hires_latent_size):
+            raise ValueError(f"hires_latent_size must be a positive int, got {hires_latent_size!r}")
+        if hires_latent_size < latent_size:
+            raise ValueError(f"hires_latent_size {hires_latent_size} is smaller than latent_size {latent_size}: the second pass upscales")
+        if inpaint_mask is not None:
+            raise ValueError("hires_latent_size does not combine with inpaint_mask: the mask and the known latents would need a second resolution")
+        if training_mode:
+            raise ValueError("hires_latent_size does not combine with training_mode=True")
+        hires_steps = timesteps if hires_timesteps is None else hires_timesteps
+        if not _is_positive_int(hires_steps):
+            raise ValueError(f"hires_timesteps must be a positive int, got {hires_timesteps!r}")
+        try:
+            strength_start(hires_steps, float(hires_strength))
+        except ValueError as e:
+            raise ValueError(f"hires_{e}") from None
+    elif hires_noise is not None:
+        raise ValueError("hires_noise needs hires_latent_size")
     if training_mode and torch.is_grad_enabled():
         # the reference back-propagates through the last denoising step (infer.py:99).  Here that differentiated call is a static
         # forward + backward plan, not a dynamic autograd graph: train.TrainStep(face_loss=..., vae=...) replays exactly this function
@@ -94,6 +148,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                                      return_tensors="pt").input_ids
 
     shape = (batch, unet.config.in_channels, latent_size, latent_size)                    # :52-59 noise on CPU, then moved
+    generator = None
     if noise is not None:
         if tuple(noise.shape) != shape:
             raise ValueError(f"noise has shape {tuple(noise.shape)}, expected {shape}")
@@ -103,6 +158,18 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     else:
         generator = torch.manual_seed(seed)
         noise = torch.randn(shape, generator=generator).to(device)
+    if hires:
+        shape2 = (batch, unet.config.in_channels, hires_latent_size, hires_latent_size)
+        if hires_noise is not None:
+            if tuple(hires_noise.shape) != shape2:
+                raise ValueError(f"hires_noise has shape {tuple(hires_noise.shape)}, expected {shape2}")
+        elif seed is None:
+            hires_noise = torch.randn(shape2)
+        else:
+            if generator is None:                     # a caller-given first noise stands for the first draw of the seeded generator
+                generator = torch.manual_seed(seed)
+                torch.randn(shape, generator=generator)
+            hires_noise = torch.randn(shape2, generator=generator)      # the draw that follows the first one
 
     inpaint = inpaint_mask is not None
     start = strength_start(timesteps, float(strength))
@@ -145,6 +212,16 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         loop.set_inpaint(lat_mask.to(device), latents0, start_noise)
     loop.reset(noise, start)
     latents = loop.run().clone()
+
+    if hires:
+        # second pass: upscale + re-noise in one launch, then the tail of a fresh schedule at the large size under the same conditioning
+        sch2 = DPMSolverMultistepScheduler.from_config(scheduler.config)
+        x_start, start2 = hires_start(latents, hires_noise.to(device), sch2, hires_steps, hires_strength)
+        loop2 = _loop_for(unet, batch, hires_latent_size, encoder_hidden_states_image.shape[1], hires_steps, guidance_scale, sch2,
+                          fusion_seed=0 if seed is None else int(seed))
+        loop2.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
+        loop2.reset(x_start, start2)
+        latents = loop2.run().clone()
 
     if vae is None:
         return latents

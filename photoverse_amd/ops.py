@@ -805,6 +805,22 @@ class Recorder:
         self._add(self.lib.pv_affine_rows_f32, _ptr(x), _ptr(y), _ptr(ca), _ptr(cb), _ptr(out), x.numel() // B, B)
         return out
 
+    def resize_bilinear_affine(self, x, size, ca=None, y=None, cb=None, out=None):
+        """out[b] = ca[b] * bilinear(x[b] -> size) (+ cb[b] * y[b]), ``F.interpolate(mode="bilinear", align_corners=False)``; x fp32 (B, C, h, w)
+        contiguous, ``size`` = (oh, ow) or one int for both, y / out fp32 (B, C, oh, ow) contiguous, ca / cb fp32 [B] (ca None = 1); ``out`` must not be ``x``."""
+        B, ch, h, w = x.shape
+        oh, ow = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        if out is None:
+            out = self.empty((B, ch, oh, ow), torch.float32)
+        assert (y is None) == (cb is None), "y and cb are given together"
+        assert tuple(out.shape) == (B, ch, oh, ow) and (y is None or tuple(y.shape) == (B, ch, oh, ow)), (x.shape, size, out.shape, None if y is None else y.shape)
+        assert all(t is None or t.numel() == B for t in (ca, cb)), (B, ca, cb)
+        assert all(t is None or (t.is_contiguous() and t.dtype == torch.float32) for t in (x, y, ca, cb, out))
+        assert out.data_ptr() != x.data_ptr(), "resize_bilinear_affine: out must not overlap x"
+        self.keep.extend(t for t in (x, y, ca, cb, out) if t is not None)
+        self._add(self.lib.pv_resize_bilinear_affine_f32, _ptr(x), _ptr(y), _ptr(ca), _ptr(cb), _ptr(out), B, ch, h, w, oh, ow)
+        return out
+
     def posterior_sample(self, moments, eps, out=None):
         """moments fp32 [B, 2c, h, w] (mean | logvar), eps fp32 [B, c, h, w] -> mean + exp(0.5 clamp(logvar)) eps."""
         B, c2 = moments.shape[0], moments.shape[1]

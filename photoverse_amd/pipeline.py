@@ -345,6 +345,10 @@ class PhotoVersePipeline:
                 latent_size = kw.get("latent_size", 64)
                 generator = torch.manual_seed(kw["seed"])
                 kw["noise"] = torch.randn((n, self.unet.config.in_channels, latent_size, latent_size), generator=generator)[sl]
+                if kw.get("hires_latent_size") is not None and kw.get("hires_noise") is None:
+                    # the second pass's noise is the NEXT draw of that generator over the global batch, as in the seeded 1-GPU run
+                    s2 = kw["hires_latent_size"]
+                    kw["hires_noise"] = torch.randn((n, self.unet.config.in_channels, s2, s2), generator=generator)[sl]
             out = run_inference(local, self.tokenizer, self.image_encoder, self.text_encoder, self.unet, self.text_adapter,
                                 self.image_adapter, self.vae, self.scheduler, self.device, list(image_encoder_layers_idx), **kw)
             return gather_latents(out, world, force=True)
