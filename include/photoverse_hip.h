@@ -478,6 +478,20 @@ int pv_step_advance(int32_t* state, void* stream);
 int pv_cfg_dpm_step_masked(const float* eps_uncond, const float* eps_cond, float* latents, float* x0_prev,
                            const float* coef, const int32_t* state, float guidance, const float* mask, const float* known,
                            const float* noise, int32_t channels, int32_t hw, int64_t n, void* stream);
+/* (ABI 19, a symbol added) pv_cfg_dpm_step / _masked with separate guidance scales and a rescale of the guided prediction.  Nothing in the
+ * reference: [EXT] the InstructPix2Pix split of classifier-free guidance and diffusers' guidance_rescale.  Per sample b over its
+ * chw = channels*hw elements, coefficient row as above:
+ *   e  = eu + g_text*(ec - eu)                          eps_image == NULL (pv_cfg_dpm_step's expression)
+ *   e  = eu + g_image*(em - eu) + g_text*(ec - em)      otherwise; em = eps(uncond text, cond image tokens)
+ *        (g_image == g_text: the em terms cancel and the first expression is evaluated - the bits of the two-forward step; em is not read)
+ *   f  = rescale*std_b(ec)/std_b(e) + (1 - rescale)     if rescale > 0 and std_b(e) > 0, else 1;   e = f*e
+ *   x0, x_next as pv_cfg_dpm_step; with mask / known / noise (all three or none) the blend of pv_cfg_dpm_step_masked.
+ * std_b: two passes (mean, then squared deviations) in fp32, one workgroup per sample, no atomics: replays are bit-identical.
+ * eps_image == NULL, rescale == 0 gives the bits of pv_cfg_dpm_step (no mask) / pv_cfg_dpm_step_masked (mask).  eps_* are read only.
+ * hw % 4 == 0, rescale in [0, 1], finite scales, batch*chw < 2^31. */
+int pv_cfg_dpm_step_guided(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
+                           const float* coef, const int32_t* state, float g_text, float g_image, float rescale, const float* mask,
+                           const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
 /* Grad-mode branch fusion of PhotoVerseAttnProcessor2_0 (attention_processor.py:413-420) WITHOUT the reference's per-layer
  * host sync (`torch.rand(1).item()`): one tiny launch draws u ~ U(0,1) per cross-attention layer on the device

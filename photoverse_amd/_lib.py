@@ -153,6 +153,8 @@ SIGNATURES = {
     "pv_cfg_dpm_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     "pv_cfg_dpm_step_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                        c_int64, c_void_p]),
+    "pv_cfg_dpm_step_guided": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_int, c_int, c_void_p]),
     "pv_step_advance": (c_int, [c_void_p, c_void_p]),
     "pv_fusion_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p]),
     "pv_cast_f32_to_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
@@ -212,7 +214,10 @@ def load():
     if lib.pv_abi_version() != ABI_VERSION:      # before the symbols are bound: a stale .so is told apart by its version, not by a missing symbol
         raise HipExtensionMissing(f"{LIB} has ABI {lib.pv_abi_version()}, expected {ABI_VERSION}: rebuild it")
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so is stale
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:     # a library of the same ABI number built before the symbol was added (pv_cfg_dpm_step_guided came without a new number)
+            raise HipExtensionMissing(f"{LIB} has no symbol {name}: it is older than this package - rebuild it with `python -m photoverse_amd.build`") from None
         fn.restype = res
         fn.argtypes = args
     _lib = lib

@@ -209,6 +209,119 @@ __global__ void cfg_dpm_step_masked_kernel(const float* eu, const float* ec, flo
     *reinterpret_cast<float4_t*>(x0p + i) = x0;
 }
 
+// Sum of a and of b over the workgroup, returned to every thread: __shfl_down inside the wave, one LDS slot per wave, then every thread adds the
+// slots in wave order.  No atomics and a fixed order: a graph replay gives the bits of an eager run.  slots: 2 x 16 floats no other reduction uses.
+__device__ __forceinline__ void pv_block_sum2(float& a, float& b, float* slots) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_down(a, o, 64);
+        b += __shfl_down(b, o, 64);
+    }
+    const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        slots[wave] = a;
+        slots[16 + wave] = b;
+    }
+    __syncthreads();
+    a = 0.f;
+    b = 0.f;
+    for (int w = 0; w < nwaves; ++w) {
+        a += slots[w];
+        b += slots[16 + w];
+    }
+}
+
+// The guided noise prediction: the two-term CFG of cfg_dpm_step_kernel (same expression), or with an image-only forward em = eps(uncond text, image
+// tokens) the split of [EXT] InstructPix2Pix  eu + g_image (em - eu) + g_text (ec - em)
+template <bool IMG>
+__device__ __forceinline__ float pv_guided_eps(float u, float m, float c, float gt, float gi) {
+    if (IMG) return u + gi * (m - u) + gt * (c - m);
+    return u + gt * (c - u);
+}
+
+// cfg_dpm_step_kernel / cfg_dpm_step_masked_kernel with the guided prediction above and [EXT] diffusers' guidance_rescale:
+//   f  = rescale * std_b(ec) / std_b(e) + (1 - rescale)      per sample b over its chw elements (f = 1 where std_b(e) == 0)
+//   e  = f * e;  x0, xn, the blend: the expressions of the two kernels above (IMG = RESCALE = false reproduces their bits)
+// One workgroup per sample, so the statistics need no second launch and no scratch: mean first, then the squared deviations (noise
+// predictions are not zero-mean), both passes over eps_* only; the last pass recomputes e and writes latents / x0_prev in place.
+template <bool IMG, bool RESCALE, bool MASK>
+__global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* eu, const float* em, const float* ec, float* lat, float* x0p,
+                                                                   const float* coef, const int32_t* state, float gt, float gi, float rescale,
+                                                                   const float* __restrict__ mask, const float* __restrict__ known,
+                                                                   const float* __restrict__ noise, long chw, int hw) {
+    __shared__ float red[4 * 16];
+    const long base = (long)blockIdx.x * chw;
+    const int nv = (int)(chw >> 2);
+    float f = 1.f;
+    if (RESCALE) {
+        float sc = 0.f, se = 0.f;
+        for (int v = threadIdx.x; v < nv; v += blockDim.x) {
+            const long i = base + (long)v * 4;
+            const float4_t u = *reinterpret_cast<const float4_t*>(eu + i);
+            const float4_t cc = *reinterpret_cast<const float4_t*>(ec + i);
+            const float4_t mm = IMG ? *reinterpret_cast<const float4_t*>(em + i) : u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                sc += cc[j];
+                se += pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi);
+            }
+        }
+        pv_block_sum2(sc, se, red);
+        const float mc = sc / (float)chw, me = se / (float)chw;
+        float qc = 0.f, qe = 0.f;
+        for (int v = threadIdx.x; v < nv; v += blockDim.x) {
+            const long i = base + (long)v * 4;
+            const float4_t u = *reinterpret_cast<const float4_t*>(eu + i);
+            const float4_t cc = *reinterpret_cast<const float4_t*>(ec + i);
+            const float4_t mm = IMG ? *reinterpret_cast<const float4_t*>(em + i) : u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float dc = cc[j] - mc, de = pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi) - me;
+                qc += dc * dc;
+                qe += de * de;
+            }
+        }
+        pv_block_sum2(qc, qe, red + 32);
+        if (qe > 0.f) f = rescale * (sqrtf(qc) / sqrtf(qe)) + (1.f - rescale);
+    }
+    const float* c = coef + (long)pv_step_index(state) * 8;
+    const float ca = c[0], cb = c[1], cx = c[2], c0 = c[3], c1 = c[4], q0 = c[5], q1 = c[6];
+    for (int v = threadIdx.x; v < nv; v += blockDim.x) {
+        const int o = v * 4;
+        const long i = base + o;
+        const float4_t u = *reinterpret_cast<const float4_t*>(eu + i);
+        const float4_t cc = *reinterpret_cast<const float4_t*>(ec + i);
+        const float4_t mm = IMG ? *reinterpret_cast<const float4_t*>(em + i) : u;
+        float4_t x = *reinterpret_cast<const float4_t*>(lat + i);
+        float4_t xp = *reinterpret_cast<const float4_t*>(x0p + i);
+        float4_t x0;
+        if (MASK) {
+            const float4_t m = *reinterpret_cast<const float4_t*>(mask + (long)blockIdx.x * hw + o % hw);
+            const float4_t kn = *reinterpret_cast<const float4_t*>(known + i);
+            const float4_t nz = *reinterpret_cast<const float4_t*>(noise + i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float e = pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi);
+                if (RESCALE) e = f * e;
+                x0[j] = ca * x[j] + cb * e;
+                const float xn = cx * x[j] + c0 * x0[j] + c1 * xp[j];
+                const float k = pv_axpby_unfused(q0, kn[j], q1, nz[j]);
+                x[j] = m[j] * xn + (1.f - m[j]) * k;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float e = pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi);
+                if (RESCALE) e = f * e;
+                x0[j] = ca * x[j] + cb * e;
+                x[j] = cx * x[j] + c0 * x0[j] + c1 * xp[j];
+            }
+        }
+        *reinterpret_cast<float4_t*>(lat + i) = x;
+        *reinterpret_cast<float4_t*>(x0p + i) = x0;
+    }
+}
+
 // out = clamp(m*gen + (1-m)*orig, lo, hi) over NCHW fp32 images, mask [B][1][hw] broadcast over the channels (hw % 4 == 0); out may be gen
 __global__ void composite_clamp_kernel(const float* gen, const float* __restrict__ orig, const float* __restrict__ mask, float* out, float lo, float hi,
                                        long chw, int hw, long n) {
@@ -675,6 +788,42 @@ extern "C" int pv_cfg_dpm_step_masked(const float* eps_uncond, const float* eps_
     hipLaunchKernelGGL(cfg_dpm_step_masked_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps_uncond,
                        eps_cond, latents, x0_prev, coef, state, guidance, mask, known, noise, (long)channels * hw, hw, (long)n);
     return PV_CHECK_LAUNCH();
+}
+
+template <bool IMG, bool RESCALE>
+static int launch_cfg_dpm_step_guided(const float* eu, const float* em, const float* ec, float* lat, float* x0p, const float* coef,
+                                      const int32_t* state, float gt, float gi, float rescale, const float* mask, const float* known,
+                                      const float* noise, int batch, long chw, int hw, hipStream_t stream) {
+    const long nv = chw / 4;
+    const dim3 grid((unsigned)batch), block((unsigned)(nv >= 1024 ? 1024 : (nv + 63) / 64 * 64));     // whole waves: every lane shuffles
+    if (mask)
+        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, true>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, gt, gi,
+                           rescale, mask, known, noise, chw, hw);
+    else
+        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, false>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, gt, gi,
+                           rescale, mask, known, noise, chw, hw);
+    return PV_CHECK_LAUNCH();
+}
+
+extern "C" int pv_cfg_dpm_step_guided(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
+                                      const float* coef, const int32_t* state, float g_text, float g_image, float rescale, const float* mask,
+                                      const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw, void* stream) {
+    if (!eps_uncond || !eps_cond || !latents || !x0_prev || !coef || !state) return (int)hipErrorInvalidValue;
+    if (batch < 1 || channels < 1 || hw < 1 || (hw % 4)) return (int)hipErrorInvalidValue;
+    if ((mask != nullptr) != (known != nullptr) || (mask != nullptr) != (noise != nullptr)) return (int)hipErrorInvalidValue;
+    if (!__builtin_isfinite(g_text) || !__builtin_isfinite(g_image) ||!(rescale >= 0.f && rescale <= 1.f)) return (int)hipErrorInvalidValue;
+    const int64_t chw = (int64_t)channels * hw, lim = (int64_t)1 << 31;
+    if (chw >= lim || (int64_t)batch * chw >= lim) return (int)hipErrorInvalidValue;
+    const hipStream_t s = (hipStream_t)stream;
+    // equal scales: the eps_image terms cancel, eu + g (em - eu) + g (ec - em) == eu + g (ec - eu).  Evaluate the two-term expression: the same
+    // polynomial with fewer roundings, so a three-forward step at equal scales has the bits of the two-forward step (eps_image is then not read)
+    if (eps_image && g_image == g_text) eps_image = nullptr;
+#define PV_GUIDED(IMG, RS) \
+    launch_cfg_dpm_step_guided<IMG, RS>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, g_text, g_image, rescale, mask, known, noise, \
+                                        batch, (long)chw, hw, s)
+    if (eps_image) return rescale > 0.f ? PV_GUIDED(true, true) : PV_GUIDED(true, false);
+    return rescale > 0.f ? PV_GUIDED(false, true) : PV_GUIDED(false, false);
+#undef PV_GUIDED
 }
 
 extern "C" int pv_composite_clamp_f32(const float* gen, const float* orig, const float* mask, float* out, float lo, float hi, int32_t batch,

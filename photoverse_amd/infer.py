@@ -14,9 +14,15 @@ latents is part of the solver-step launch (``pv_cfg_dpm_step_masked``) - and ``p
 Also beyond the reference ([EXT] the two-pass "hires fix" of A1111 / diffusers' latent upscale): with ``hires_latent_size`` the image is generated at
 ``latent_size`` (SD-v1.5 was trained at 64), its latents are upscaled and re-noised part-way up the schedule - ``hires_start``, one launch of
 ``pv_resize_bilinear_affine_f32`` - and only the last ``hires_strength`` of the schedule runs at the large size, on a second cached ``DenoiseLoop``.
+
+And control over the guidance itself ([EXT] the InstructPix2Pix split of classifier-free guidance, diffusers' ``guidance_rescale``):
+``image_guidance_scale`` gives the image-token branch (identity) a scale of its own beside ``guidance_scale`` (the prompt) at the price of a third forward
+per step, ``guidance_rescale`` renormalises the guided prediction to the conditional one's per-sample standard deviation; both are part of the solver-step
+launch (``pv_cfg_dpm_step_guided``).
 """
 from __future__ import annotations
 
+import math
 import numbers
 from collections import OrderedDict
 
@@ -42,6 +48,10 @@ def strength_start(timesteps: int, strength: float) -> int:
 
 def _is_positive_int(v) -> bool:
     return isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 1
+
+
+def _is_finite_real(v) -> bool:
+    return isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v)
 
 
 def hires_start(latents: torch.Tensor, noise: torch.Tensor, scheduler, timesteps: int, strength: float):
@@ -78,13 +88,15 @@ def latent_mask(inpaint_mask: torch.Tensor, batch: int, latent_size: int):
     return pix, lat
 
 
-def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False) -> DenoiseLoop:
+def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False,
+              image_guidance=None, guidance_rescale=0.0) -> DenoiseLoop:
     cache = unet.__dict__.setdefault("_denoise_loops", OrderedDict())
-    key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed), bool(inpaint))
+    key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed),
+           None if image_guidance is None else float(image_guidance), float(guidance_rescale), bool(inpaint))
     loop = cache.pop(key, None)
     if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0):
         loop = DenoiseLoop(unet, batch, latent_size, n_ip, steps, guidance, scheduler=scheduler, training_mode=training_mode,
-                           fusion_seed=fusion_seed, inpaint=inpaint)
+                           fusion_seed=fusion_seed, inpaint=inpaint, image_guidance_scale=image_guidance, guidance_rescale=guidance_rescale)
         loop.unet_version = unet.__dict__.get("_pack_version", 0)
     cache[key] = loop                               # most recently used last
     while len(cache) > MAX_CACHED_LOOPS:
@@ -95,7 +107,8 @@ def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, traini
 def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler,
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
-                  inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
+                  image_guidance_scale=None, guidance_rescale=0.0, inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5,
+                  hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
     global batch once and hands each rank its slice.
@@ -109,7 +122,23 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     ``hires_start`` with ``hires_strength`` in (0, 1] of a schedule of ``hires_timesteps`` steps (None: ``timesteps``), and the last
     ``int(hires_timesteps * hires_strength)`` steps run at the large size under the same conditioning; the result is decoded at that size.
     ``hires_noise`` (B, C, hires_latent_size, hires_latent_size): the noise of the second pass; otherwise it is drawn right after the first one from the
-    same generator (``seed``) or with ``torch.randn``.  Not with ``inpaint_mask`` or ``training_mode``."""
+    same generator (``seed``) or with ``torch.randn``.  Not with ``inpaint_mask`` or ``training_mode``.
+
+    ``image_guidance_scale`` (None: one scale, as ever): the noise prediction becomes ``eps_u + image_guidance_scale (eps_m - eps_u) + guidance_scale
+    (eps_c - eps_m)`` with ``eps_m`` a third forward per step under (negative prompt, image tokens of the input image) - how strongly the result keeps
+    the identity and how strongly it follows the prompt are set apart.  A value equal to ``guidance_scale`` is the ordinary formula and runs the ordinary
+    two-forward loop.  ``guidance_rescale`` in [0, 1] (0: off): the guided prediction of every sample is scaled by
+    ``guidance_rescale * std(eps_c) / std(eps) + 1 - guidance_rescale``, against the over-saturation of high scales.  Both hold for the second pass of
+    a hires run and for ``inpaint_mask``; neither combines with ``training_mode``."""
+    if image_guidance_scale is not None and not _is_finite_real(image_guidance_scale):      # before any model is touched
+        raise ValueError(f"image_guidance_scale must be a finite number or None, got {image_guidance_scale!r}")
+    if not _is_finite_real(guidance_rescale) or not 0.0 <= guidance_rescale <= 1.0:
+        raise ValueError(f"guidance_rescale must be a number in [0, 1], got {guidance_rescale!r}")
+    if training_mode and (image_guidance_scale is not None or guidance_rescale > 0):
+        raise ValueError("image_guidance_scale / guidance_rescale do not combine with training_mode=True")
+    if image_guidance_scale is not None and float(image_guidance_scale) == float(guidance_scale):
+        image_guidance_scale = None                    # the ordinary formula: two forwards
+    guide = dict(image_guidance=image_guidance_scale, guidance_rescale=float(guidance_rescale))
     hires = hires_latent_size is not None
     if hires:                                          # before anything else: the first pass must not run for a second one that cannot
         if not _is_positive_int(hires_latent_size):
@@ -206,7 +235,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                                           "concept_placeholder_idx": placeholder_idx})[0]
 
     loop = _loop_for(unet, batch, latent_size, encoder_hidden_states_image.shape[1], timesteps, guidance_scale, sch,     # :98-119
-                     training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint)
+                     training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint, **guide)
     loop.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
     if inpaint:
         loop.set_inpaint(lat_mask.to(device), latents0, start_noise)
@@ -218,7 +247,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         sch2 = DPMSolverMultistepScheduler.from_config(scheduler.config)
         x_start, start2 = hires_start(latents, hires_noise.to(device), sch2, hires_steps, hires_strength)
         loop2 = _loop_for(unet, batch, hires_latent_size, encoder_hidden_states_image.shape[1], hires_steps, guidance_scale, sch2,
-                          fusion_seed=0 if seed is None else int(seed))
+                          fusion_seed=0 if seed is None else int(seed), **guide)
         loop2.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
         loop2.reset(x_start, start2)
         latents = loop2.run().clone()

@@ -31,7 +31,8 @@ class DenoiseLoop:
     def __init__(self, unet, batch: int, latent_size: int, n_ip: int, num_steps: int, guidance_scale: float,
                  scheduler: Optional[DPMSolverMultistepScheduler] = None, n_text: int = 77, use_graph: bool = True,
                  two_streams: bool = True, batch_splits: int = 1, training_mode: bool = False, fusion_seed: int = 0,
-                 merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False):
+                 merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False,
+                 image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0):
         """``training_mode``: the reference enables grad on the LAST denoising step only (infer.py:99), where every cross-attention
         layer of both forwards then draws its branch fusion (attention_processor.py:413-420).  Here the draw runs on the device inside
         the captured step (``pv_fusion_draw`` keyed on the step counter), so the same graph serves all steps.  This is the forward semantics
@@ -50,13 +51,31 @@ class DenoiseLoop:
         ``inpaint`` (beyond the reference; [EXT] diffusers' inpainting with a 4-channel UNet): the solver step of the tail becomes
         ``pv_cfg_dpm_step_masked`` - still one launch - which keeps the latents where ``mask`` is 0 on ``known`` noised with ``noise`` to the step's
         next timestep (the clean ``known`` after the last step).  The three static buffers are filled by ``set_inpaint``; a mask of ones (the
-        initial content) is the plain loop."""
+        initial content) is the plain loop.
+
+        ``image_guidance_scale`` / ``guidance_rescale`` (beyond the reference; [EXT] the InstructPix2Pix split of classifier-free guidance and diffusers'
+        ``guidance_rescale``).  At their defaults (None, 0.0) the loop is the one described above: same engines, same tail launcher.  With
+        ``guidance_rescale`` in (0, 1] alone the two forwards stay as they are and the solver step of the tail becomes ``pv_cfg_dpm_step_guided``, which
+        scales the guided prediction of every sample to ``rescale * std(eps_cond) / std(eps) + 1 - rescale``.  With ``image_guidance_scale`` a third
+        forward (uncond text, cond image tokens -> ``eps_m``) runs per step and the prediction is
+        ``eps_u + image_guidance_scale (eps_m - eps_u) + guidance_scale (eps_c - eps_m)``: the image-token branch (identity) and the prompt get a scale
+        each (at equal scales the ``eps_m`` terms cancel and the launcher evaluates the two-term expression: the bits of the two-forward loop).  The third engine reads the ``text_u`` / ``ip_c`` buffers of the other two, so ``set_conditioning`` is unchanged.  In this mode the three
+        forwards are three whole plans (``merge_lowres`` is off) on the main and two side streams - three parallel branches of the captured graph;
+        ``share_prefix`` still applies (all three start from the one prefix plan).  Not with ``training_mode``.  ``inpaint`` goes through the same
+        launcher's mask arguments."""
         dev = unet.device
         if dev.type != "cuda":
             raise RuntimeError("DenoiseLoop needs the UNet on a HIP device (no CPU path)")
         self.unet, self.B, self.S, self.P, self.T = unet, batch, latent_size, n_ip, num_steps
         self.guidance = float(guidance_scale)
         self.training_mode = bool(training_mode)
+        self.image_guidance = None if image_guidance_scale is None else float(image_guidance_scale)
+        self.guidance_rescale = float(guidance_rescale)
+        if not 0.0 <= self.guidance_rescale <= 1.0:
+            raise ValueError(f"guidance_rescale must be in [0, 1], got {guidance_rescale}")
+        three = self.image_guidance is not None
+        if three and training_mode:
+            raise ValueError("image_guidance_scale does not combine with training_mode=True")
         sch = scheduler if scheduler is not None else DPMSolverMultistepScheduler()
         sch.set_timesteps(num_steps)
         self.scheduler = sch
@@ -84,7 +103,8 @@ class DenoiseLoop:
         sb = batch // batch_splits
         self.eps_u = torch.empty_like(self.latents)
         self.eps_c = torch.empty_like(self.latents)
-        self.engines_u, self.engines_c, self.engines_m, self.engines_p = [], [], [], []
+        self.eps_m = torch.empty_like(self.latents) if three else None      # eps(uncond text, cond image tokens)
+        self.engines_u, self.engines_c, self.engines_m, self.engines_p, self.engines_i = [], [], [], [], []
         if share_prefix is None:
             share_prefix = os.environ.get("PV_SHARE_PREFIX", "0") == "1"
         first = unet.down_blocks[0]
@@ -104,7 +124,7 @@ class DenoiseLoop:
             rows = 2 * batch * (latent_size >> split) ** 2
             # (... and at the launch-bound end, up to 1024 rows - bs = 1 / 2 at 64 x 64 latents - the merged plan's fewer launches win again: +1.0 % / +0.4 %)
             merge_lowres = (env != "0") if env is not None else (rows >= _MERGE_MIN_ROWS or rows <= 1024)
-        self.merge_lowres = bool(merge_lowres and not training_mode and batch_splits == 1 and n_lv > split
+        self.merge_lowres = bool(merge_lowres and not training_mode and not three and batch_splits == 1 and n_lv > split
                                  and ((latent_size >> split) ** 2) % 64 == 0 and latent_size % (1 << (n_lv - 1)) == 0)
         if self.merge_lowres:
             # text / image-token buffers of the two branches are the halves of ONE buffer: the merged plan reads it whole
@@ -141,12 +161,20 @@ class DenoiseLoop:
                                               ip=self.ip_u[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_u[sl], **kw, **fs))
             self.engines_c.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_c[i * sb * n_text:(i + 1) * sb * n_text],
                                               ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_c[sl], **kw, **fs2))
+            if three:
+                self.engines_i.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_u[i * sb * n_text:(i + 1) * sb * n_text],
+                                                  ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_m[sl], **kw))
         self.eng_u, self.eng_c = self.engines_u[0], self.engines_c[0]
         self.tail = Recorder(dev)
         if self.inpaint:
             self.mask = torch.ones((batch, 1, latent_size, latent_size), dtype=f32, device=dev)
             self.known = torch.zeros_like(self.latents)
             self.noise = torch.zeros_like(self.latents)
+        if three or self.guidance_rescale > 0.0:
+            blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
+            self.tail.cfg_dpm_step_guided(self.eps_u, self.eps_m, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
+                                          self.image_guidance, self.guidance_rescale, **blend)
+        elif self.inpaint:
             self.tail.cfg_dpm_step_masked(self.eps_u, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
                                           self.mask, self.known, self.noise)
         else:
@@ -155,14 +183,15 @@ class DenoiseLoop:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.use_graph = use_graph
         self.two_streams = two_streams
-        n_side = (2 * batch_splits - 1) if two_streams else 0
+        n_side = ((3 if three else 2) * batch_splits - 1) if two_streams else 0
         self._sides = [torch.cuda.Stream(device=dev) for _ in range(n_side)]
         self.launches_per_step = sum(len(e.rec) for e in self.all_engines) + len(self.tail)
 
     @property
     def all_engines(self):
-        """Every plan of a step (uncond / cond branches and, with ``merge_lowres``, the merged low-resolution part)."""
-        return self.engines_u + self.engines_c + self.engines_m + self.engines_p
+        """Every plan of a step (uncond / cond branches, with ``merge_lowres`` the merged low-resolution part, with ``image_guidance_scale`` the
+        image-only branch)."""
+        return self.engines_u + self.engines_c + self.engines_m + self.engines_p + self.engines_i
 
     # ------------------------------------------------------------------
     def set_conditioning(self, cond: Tuple[torch.Tensor, torch.Tensor], uncond: Tuple[torch.Tensor, torch.Tensor]):
@@ -229,11 +258,11 @@ class DenoiseLoop:
             self.tail.run()
             return
         if self.two_streams:
-            # the unconditional and conditional forwards are independent until the CFG combine: fork them onto two HIP
-            # streams (two parallel branches of the captured graph) so the small low-resolution launches of one overlap
-            # the other's; joined before the combine
+            # the forwards of a step (uncond, cond, with image_guidance_scale the image-only one; each per sub-batch) are independent until the
+            # CFG combine: fork them onto HIP streams (parallel branches of the captured graph) so the small low-resolution launches of one
+            # overlap the others'; joined before the combine
             main = torch.cuda.current_stream()
-            engines = self.engines_u + self.engines_c
+            engines = self.engines_u + self.engines_c + self.engines_i
             for side, eng in zip(self._sides, engines[1:]):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
@@ -242,7 +271,7 @@ class DenoiseLoop:
             for side in self._sides:
                 main.wait_stream(side)
         else:
-            for e in self.engines_u + self.engines_c:
+            for e in self.engines_u + self.engines_c + self.engines_i:
                 e.rec.run()
         self.tail.run()
 
