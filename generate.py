@@ -10,7 +10,8 @@ still comes from ``--input_image_path``), ``--strength`` (img2img: run only the 
 ``--hires_latent_size`` (two-pass high-resolution generation: generate at ``--latent_size``, upscale the latents, re-noise them and run the last
 ``--hires_strength`` of a ``--hires_timesteps`` schedule at the large size; the images are ``8 * hires_latent_size`` pixels);
 ``--image_guidance_scale`` (a guidance scale of its own for the identity - the image tokens - beside ``--guidance_scale`` for the prompt: a third
-forward per step) and ``--guidance_rescale`` (renormalise the guided prediction against the over-saturation of high scales).
+forward per step) and ``--guidance_rescale`` (renormalise the guided prediction against the over-saturation of high scales);
+``--sampler sde-dpmsolver++`` (the stochastic form of the solver, "DPM++ 2M SDE": fresh noise at every step, keyed on ``--seed``).
 """
 import argparse
 import os
@@ -53,6 +54,8 @@ parser.add_argument("--image_guidance_scale", type=float, default=None,
                     help="Guidance scale of the image tokens (identity); --guidance_scale then weighs the prompt alone (default: one scale for both)")
 parser.add_argument("--guidance_rescale", type=float, default=0.0,
                     help="In [0, 1]: scale the guided noise prediction towards the conditional one's standard deviation (0 = off)")
+parser.add_argument("--sampler", choices=["dpmsolver++", "sde-dpmsolver++"], default="dpmsolver++",
+                    help="dpmsolver++: deterministic DPM-Solver++(2M); sde-dpmsolver++: its stochastic form (fresh noise per step, drawn on the device)")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -124,7 +127,8 @@ if __name__ == "__main__":
                             timesteps=args.num_timesteps, from_noised_image=args.from_noised_image, seed=args.seed,
                             strength=args.strength, inpaint_mask=prepare_mask(args), paste_back=not args.no_paste_back,
                             hires_latent_size=args.hires_latent_size, hires_strength=args.hires_strength, hires_timesteps=args.hires_timesteps,
-                            image_guidance_scale=args.image_guidance_scale, guidance_rescale=args.guidance_rescale)
+                            image_guidance_scale=args.image_guidance_scale, guidance_rescale=args.guidance_rescale,
+                            sampler=args.sampler)
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

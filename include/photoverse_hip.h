@@ -492,6 +492,26 @@ int pv_cfg_dpm_step_masked(const float* eps_uncond, const float* eps_cond, float
 int pv_cfg_dpm_step_guided(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
                            const float* coef, const int32_t* state, float g_text, float g_image, float rescale, const float* mask,
                            const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw, void* stream);
+/* (ABI 19, a symbol added) pv_cfg_dpm_step_guided as the step of the STOCHASTIC solver SDE-DPM-Solver++(2M) ([EXT] diffusers'
+ * algorithm_type="sde-dpmsolver++", first-order and midpoint second-order updates): the guided step above, then
+ *   xn += cn * z        cn = column 7 of the coefficient row {ca, cb, cx, c0, c1, q0, q1, cn}, z ~ N(0, I) fresh per step
+ * before the inpainting blend (the kept region stays on the re-noised known latents); x0_prev gets x0 as before.  The rows of the SDE table
+ * (scheduler.coefficient_table of that type), h = lambda_t - lambda_s, r0 = h_prev / h:
+ *   A = alpha_t (1 - exp(-2h)),  cx = (sigma_t / sigma_s) exp(-h),  cn = sigma_t sqrt(1 - exp(-2h))
+ *   first order: c0 = A, c1 = 0;   second order: c0 = A (1 + 1/(2 r0)), c1 = -A / (2 r0);   last row (sigma_t = 0): cx = 0, c0 = 1, c1 = 0, cn = 0.
+ * The noise is generated in the kernel and is part of the interface.  rng = four device words {seed_lo, seed_hi, sample_offset, stream}.  The
+ * thread that owns elements 4q .. 4q+3 of sample b (q = offset inside the sample's chw elements / 4) evaluates one Philox4x32-10 block with
+ *   key (seed_lo, seed_hi),  counter (q, sample_offset + b, step, stream),  step = the clamped step index of `state`
+ * and turns its words w0..w3 into four normals by Box-Muller:
+ *   u_k = ((w_k >> 9) + 0.5) * 2^-23                      exact in fp32, strictly inside (0, 1)
+ *   z0 = r0 cos(2 pi u1), z1 = r0 sin(2 pi u1), r0 = sqrt(-2 ln u0);   z2 = r1 cos(2 pi u3), z3 = r1 sin(2 pi u3), r1 = sqrt(-2 ln u2)
+ * (sincospif(2 u), accurate logf).  Everything the noise depends on is contents of device buffers - the step counter and rng -, so a captured
+ * launch serves any seed, start row and batch offset; no atomics: a replay gives the bits of an eager run.  Sample b at sample_offset s gets the
+ * noise of sample 0 at sample_offset s + b.  rng must not be NULL; every other argument and limit as pv_cfg_dpm_step_guided. */
+int pv_cfg_dpm_step_stochastic(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
+                               const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float rescale,
+                               const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
+                               void* stream);
 
 /* Grad-mode branch fusion of PhotoVerseAttnProcessor2_0 (attention_processor.py:413-420) WITHOUT the reference's per-layer
  * host sync (`torch.rand(1).item()`): one tiny launch draws u ~ U(0,1) per cross-attention layer on the device

@@ -209,6 +209,34 @@ __global__ void cfg_dpm_step_masked_kernel(const float* eu, const float* ec, flo
     *reinterpret_cast<float4_t*>(x0p + i) = x0;
 }
 
+// Philox4x32-10 (Salmon et al. 2011): counter-based - a draw is a function of (key, counter) alone, no stored stream
+struct philox_block { uint32_t w[4]; };
+__device__ __forceinline__ philox_block philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return philox_block{{c0, c1, c2, c3}};
+}
+
+// Four standard normals from one Philox block by Box-Muller (part of pv_cfg_dpm_step_stochastic's interface, restated in numpy by the tests):
+//   u_k = ((w_k >> 9) + 0.5) * 2^-23      exact in fp32, strictly inside (0, 1): the logarithm is finite
+//   z0, z1 = sqrt(-2 ln u0) * (cos, sin)(2 pi u1);   z2, z3 = sqrt(-2 ln u2) * (cos, sin)(2 pi u3)
+// sincospif(2 u) reduces the argument exactly (no rounded 2 pi); logf / sqrtf are the accurate ones.
+__device__ __forceinline__ float4_t pv_normal4(const philox_block& p) {
+    float u[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = ((float)(p.w[k] >> 9) + 0.5f) * (1.0f / 8388608.0f);
+    const float r0 = sqrtf(-2.f * logf(u[0])), r1 = sqrtf(-2.f * logf(u[2]));
+    float s0, c0, s1, c1;
+    sincospif(2.f * u[1], &s0, &c0);
+    sincospif(2.f * u[3], &s1, &c1);
+    return float4_t{r0 * c0, r0 * s0, r1 * c1, r1 * s1};
+}
+
 // Sum of a and of b over the workgroup, returned to every thread: __shfl_down inside the wave, one LDS slot per wave, then every thread adds the
 // slots in wave order.  No atomics and a fixed order: a graph replay gives the bits of an eager run.  slots: 2 x 16 floats no other reduction uses.
 __device__ __forceinline__ void pv_block_sum2(float& a, float& b, float* slots) {
@@ -241,14 +269,18 @@ __device__ __forceinline__ float pv_guided_eps(float u, float m, float c, float 
 
 // cfg_dpm_step_kernel / cfg_dpm_step_masked_kernel with the guided prediction above and [EXT] diffusers' guidance_rescale:
 //   f  = rescale * std_b(ec) / std_b(e) + (1 - rescale)      per sample b over its chw elements (f = 1 where std_b(e) == 0)
-//   e  = f * e;  x0, xn, the blend: the expressions of the two kernels above (IMG = RESCALE = false reproduces their bits)
+//   e  = f * e;  x0, xn, the blend: the expressions of the two kernels above (IMG = RESCALE = NOISE = false reproduces their bits)
+// NOISE (pv_cfg_dpm_step_stochastic, the SDE form of the solver): xn += cn * z before the blend, cn = column 7 of the row, z the four normals of the
+// Philox block keyed (rng[0], rng[1]) at counter (float4 index inside the sample, rng[2] + sample, step index, rng[3]).  Everything z depends
+// on is contents of device buffers, so a captured launch serves any seed / start row / batch offset, and a replay gives the bits of an eager run.
 // One workgroup per sample, so the statistics need no second launch and no scratch: mean first, then the squared deviations (noise
 // predictions are not zero-mean), both passes over eps_* only; the last pass recomputes e and writes latents / x0_prev in place.
-template <bool IMG, bool RESCALE, bool MASK>
+template <bool IMG, bool RESCALE, bool MASK, bool NOISE>
 __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* eu, const float* em, const float* ec, float* lat, float* x0p,
-                                                                   const float* coef, const int32_t* state, float gt, float gi, float rescale,
-                                                                   const float* __restrict__ mask, const float* __restrict__ known,
-                                                                   const float* __restrict__ noise, long chw, int hw) {
+                                                                   const float* coef, const int32_t* state, const uint32_t* __restrict__ rng,
+                                                                   float gt, float gi, float rescale, const float* __restrict__ mask,
+                                                                   const float* __restrict__ known, const float* __restrict__ noise, long chw,
+                                                                   int hw) {
     __shared__ float red[4 * 16];
     const long base = (long)blockIdx.x * chw;
     const int nv = (int)(chw >> 2);
@@ -284,8 +316,15 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
         pv_block_sum2(qc, qe, red + 32);
         if (qe > 0.f) f = rescale * (sqrtf(qc) / sqrtf(qe)) + (1.f - rescale);
     }
-    const float* c = coef + (long)pv_step_index(state) * 8;
+    const int step = pv_step_index(state);
+    const float* c = coef + (long)step * 8;
     const float ca = c[0], cb = c[1], cx = c[2], c0 = c[3], c1 = c[4], q0 = c[5], q1 = c[6];
+    float cn = 0.f;
+    uint32_t k0 = 0u, k1 = 0u, sample = 0u, stream = 0u;
+    if (NOISE) {
+        cn = c[7];
+        k0 = rng[0]; k1 = rng[1]; sample = rng[2] + blockIdx.x; stream = rng[3];
+    }
     for (int v = threadIdx.x; v < nv; v += blockDim.x) {
         const int o = v * 4;
         const long i = base + o;
@@ -295,6 +334,8 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
         float4_t x = *reinterpret_cast<const float4_t*>(lat + i);
         float4_t xp = *reinterpret_cast<const float4_t*>(x0p + i);
         float4_t x0;
+        float4_t z = {0.f, 0.f, 0.f, 0.f};
+        if (NOISE) z = pv_normal4(philox4x32_10(k0, k1, (uint32_t)v, sample, (uint32_t)step, stream));
         if (MASK) {
             const float4_t m = *reinterpret_cast<const float4_t*>(mask + (long)blockIdx.x * hw + o % hw);
             const float4_t kn = *reinterpret_cast<const float4_t*>(known + i);
@@ -304,7 +345,8 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
                 float e = pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi);
                 if (RESCALE) e = f * e;
                 x0[j] = ca * x[j] + cb * e;
-                const float xn = cx * x[j] + c0 * x0[j] + c1 * xp[j];
+                float xn = cx * x[j] + c0 * x0[j] + c1 * xp[j];
+                if (NOISE) xn += cn * z[j];
                 const float k = pv_axpby_unfused(q0, kn[j], q1, nz[j]);
                 x[j] = m[j] * xn + (1.f - m[j]) * k;
             }
@@ -315,6 +357,7 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
                 if (RESCALE) e = f * e;
                 x0[j] = ca * x[j] + cb * e;
                 x[j] = cx * x[j] + c0 * x0[j] + c1 * xp[j];
+                if (NOISE) x[j] += cn * z[j];
             }
         }
         *reinterpret_cast<float4_t*>(lat + i) = x;
@@ -340,17 +383,9 @@ __global__ void composite_clamp_kernel(const float* gen, const float* __restrict
 
 __global__ void step_advance_kernel(int32_t* state) { state[0] += 1; }
 
-// Philox4x32-10 (Salmon et al. 2011): counter-based, so one launch = one independent draw per layer with no stored stream
+// the draws of pv_fusion_draw: counter (c0, c1, 0, 0), first word of the block
 __device__ __forceinline__ uint32_t philox_first_word(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1) {
-    uint32_t c2 = 0u, c3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
+    return philox4x32_10(k0, k1, c0, c1, 0u, 0u).w[0];
 }
 
 __global__ void fusion_draw_kernel(const int32_t* state, uint32_t* rng, const float* forced, float* out, int n, float r1, float r2,
@@ -790,25 +825,28 @@ extern "C" int pv_cfg_dpm_step_masked(const float* eps_uncond, const float* eps_
     return PV_CHECK_LAUNCH();
 }
 
-template <bool IMG, bool RESCALE>
+template <bool IMG, bool RESCALE, bool NOISE>
 static int launch_cfg_dpm_step_guided(const float* eu, const float* em, const float* ec, float* lat, float* x0p, const float* coef,
-                                      const int32_t* state, float gt, float gi, float rescale, const float* mask, const float* known,
-                                      const float* noise, int batch, long chw, int hw, hipStream_t stream) {
+                                      const int32_t* state, const uint32_t* rng, float gt, float gi, float rescale, const float* mask,
+                                      const float* known, const float* noise, int batch, long chw, int hw, hipStream_t stream) {
     const long nv = chw / 4;
     const dim3 grid((unsigned)batch), block((unsigned)(nv >= 1024 ? 1024 : (nv + 63) / 64 * 64));     // whole waves: every lane shuffles
     if (mask)
-        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, true>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, gt, gi,
-                           rescale, mask, known, noise, chw, hw);
+        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, true, NOISE>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, rng,
+                           gt, gi, rescale, mask, known, noise, chw, hw);
     else
-        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, false>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, gt, gi,
-                           rescale, mask, known, noise, chw, hw);
+        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, false, NOISE>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, rng,
+                           gt, gi, rescale, mask, known, noise, chw, hw);
     return PV_CHECK_LAUNCH();
 }
 
-extern "C" int pv_cfg_dpm_step_guided(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
-                                      const float* coef, const int32_t* state, float g_text, float g_image, float rescale, const float* mask,
-                                      const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw, void* stream) {
-    if (!eps_uncond || !eps_cond || !latents || !x0_prev || !coef || !state) return (int)hipErrorInvalidValue;
+// the body of pv_cfg_dpm_step_guided (rng == NULL) and pv_cfg_dpm_step_stochastic (rng != NULL): validation before the first HIP call
+template <bool NOISE>
+static int cfg_dpm_step_guided_entry(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
+                                     const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float rescale,
+                                     const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
+                                     void* stream) {
+    if (!eps_uncond || !eps_cond || !latents || !x0_prev || !coef || !state || (NOISE && !rng)) return (int)hipErrorInvalidValue;
     if (batch < 1 || channels < 1 || hw < 1 || (hw % 4)) return (int)hipErrorInvalidValue;
     if ((mask != nullptr) != (known != nullptr) || (mask != nullptr) != (noise != nullptr)) return (int)hipErrorInvalidValue;
     if (!__builtin_isfinite(g_text) || !__builtin_isfinite(g_image) ||!(rescale >= 0.f && rescale <= 1.f)) return (int)hipErrorInvalidValue;
@@ -819,11 +857,26 @@ extern "C" int pv_cfg_dpm_step_guided(const float* eps_uncond, const float* eps_
     // polynomial with fewer roundings, so a three-forward step at equal scales has the bits of the two-forward step (eps_image is then not read)
     if (eps_image && g_image == g_text) eps_image = nullptr;
 #define PV_GUIDED(IMG, RS) \
-    launch_cfg_dpm_step_guided<IMG, RS>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, g_text, g_image, rescale, mask, known, noise, \
-                                        batch, (long)chw, hw, s)
+    launch_cfg_dpm_step_guided<IMG, RS, NOISE>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, rng, g_text, g_image, rescale, mask, \
+                                               known, noise, batch, (long)chw, hw, s)
     if (eps_image) return rescale > 0.f ? PV_GUIDED(true, true) : PV_GUIDED(true, false);
     return rescale > 0.f ? PV_GUIDED(false, true) : PV_GUIDED(false, false);
 #undef PV_GUIDED
+}
+
+extern "C" int pv_cfg_dpm_step_guided(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
+                                      const float* coef, const int32_t* state, float g_text, float g_image, float rescale, const float* mask,
+                                      const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw, void* stream) {
+    return cfg_dpm_step_guided_entry<false>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, nullptr, g_text, g_image, rescale, mask,
+                                            known, noise, batch, channels, hw, stream);
+}
+
+extern "C" int pv_cfg_dpm_step_stochastic(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
+                                          const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float rescale,
+                                          const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
+                                          void* stream) {
+    return cfg_dpm_step_guided_entry<true>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, rng, g_text, g_image, rescale, mask,
+                                           known, noise, batch, channels, hw, stream);
 }
 
 extern "C" int pv_composite_clamp_f32(const float* gen, const float* orig, const float* mask, float* out, float lo, float hi, int32_t batch,

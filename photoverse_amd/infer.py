@@ -19,6 +19,10 @@ And control over the guidance itself ([EXT] the InstructPix2Pix split of classif
 ``image_guidance_scale`` gives the image-token branch (identity) a scale of its own beside ``guidance_scale`` (the prompt) at the price of a third forward
 per step, ``guidance_rescale`` renormalises the guided prediction to the conditional one's per-sample standard deviation; both are part of the solver-step
 launch (``pv_cfg_dpm_step_guided``).
+
+And the sampler ([EXT] diffusers' ``algorithm_type="sde-dpmsolver++"``, the "DPM++ 2M SDE" of the front ends): ``sampler="sde-dpmsolver++"`` runs the
+stochastic form of the solver, whose fresh noise per step is generated inside the solver-step launch (``pv_cfg_dpm_step_stochastic``) from a Philox
+stream keyed on ``seed``, the global sample index and the device-resident step counter - the captured graph is the same for every step and seed.
 """
 from __future__ import annotations
 
@@ -88,15 +92,25 @@ def latent_mask(inpaint_mask: torch.Tensor, batch: int, latent_size: int):
     return pix, lat
 
 
+SAMPLERS = ("dpmsolver++", "sde-dpmsolver++")
+
+
+def _scheduler_for(scheduler, sampler) -> DPMSolverMultistepScheduler:
+    """infer.py:39-40 - the sampler is rebuilt from the loaded scheduler's config on every call; ``sampler`` sets its algorithm type."""
+    return DPMSolverMultistepScheduler.from_config(scheduler.config, algorithm_type=sampler)
+
+
 def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False,
               image_guidance=None, guidance_rescale=0.0) -> DenoiseLoop:
     cache = unet.__dict__.setdefault("_denoise_loops", OrderedDict())
+    stochastic = bool(getattr(scheduler, "stochastic", False))      # the sampler: part of the key through the scheduler run_inference built for it
     key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed),
-           None if image_guidance is None else float(image_guidance), float(guidance_rescale), bool(inpaint))
+           None if image_guidance is None else float(image_guidance), float(guidance_rescale), stochastic, bool(inpaint))
     loop = cache.pop(key, None)
     if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0):
         loop = DenoiseLoop(unet, batch, latent_size, n_ip, steps, guidance, scheduler=scheduler, training_mode=training_mode,
-                           fusion_seed=fusion_seed, inpaint=inpaint, image_guidance_scale=image_guidance, guidance_rescale=guidance_rescale)
+                           fusion_seed=fusion_seed, inpaint=inpaint, image_guidance_scale=image_guidance, guidance_rescale=guidance_rescale,
+                           stochastic=stochastic)
         loop.unet_version = unet.__dict__.get("_pack_version", 0)
     cache[key] = loop                               # most recently used last
     while len(cache) > MAX_CACHED_LOOPS:
@@ -107,8 +121,8 @@ def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, traini
 def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler,
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
-                  image_guidance_scale=None, guidance_rescale=0.0, inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5,
-                  hires_timesteps=None, hires_noise=None):
+                  image_guidance_scale=None, guidance_rescale=0.0, sampler="dpmsolver++", sample_offset=0, inpaint_mask=None, paste_back=True,
+                  hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
     global batch once and hands each rank its slice.
@@ -129,7 +143,22 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     the identity and how strongly it follows the prompt are set apart.  A value equal to ``guidance_scale`` is the ordinary formula and runs the ordinary
     two-forward loop.  ``guidance_rescale`` in [0, 1] (0: off): the guided prediction of every sample is scaled by
     ``guidance_rescale * std(eps_c) / std(eps) + 1 - guidance_rescale``, against the over-saturation of high scales.  Both hold for the second pass of
-    a hires run and for ``inpaint_mask``; neither combines with ``training_mode``."""
+    a hires run and for ``inpaint_mask``; neither combines with ``training_mode``.
+
+    ``sampler``: ``"dpmsolver++"`` (the reference's deterministic DPM-Solver++(2M)) or ``"sde-dpmsolver++"`` (its stochastic form: fresh noise at every
+    step, drawn on the device).  The noise stream's seed is ``seed`` when given, otherwise one ``torch.randint`` draw from the default CPU generator
+    taken after the start-noise draws (the start noise of an unseeded call is what it was); the first pass draws from stream 0, the second pass of a
+    hires run from stream 1.  ``sample_offset`` (int >= 0): the global index of this call's first sample - sample ``b`` gets the per-step noise sample
+    ``sample_offset + b`` of a whole-batch call gets (``PhotoVersePipeline(shard=True)`` passes the rank's offset).  That equivalence needs ``seed``:
+    unseeded, every call - every rank of a sharded run - draws a key of its own.  The kept region of an
+    ``inpaint_mask`` run keeps its one static noise.  Not with ``training_mode``."""
+    if sampler not in SAMPLERS:                                                             # before any model is touched
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if not (isinstance(sample_offset, numbers.Integral) and not isinstance(sample_offset, bool) and 0 <= sample_offset < (1 << 32)):
+        raise ValueError(f"sample_offset must be an int in [0, 2^32), got {sample_offset!r}")
+    stochastic = sampler == "sde-dpmsolver++"
+    if stochastic and training_mode:
+        raise ValueError("sampler='sde-dpmsolver++' does not combine with training_mode=True")
     if image_guidance_scale is not None and not _is_finite_real(image_guidance_scale):      # before any model is touched
         raise ValueError(f"image_guidance_scale must be a finite number or None, got {image_guidance_scale!r}")
     if not _is_finite_real(guidance_rescale) or not 0.0 <= guidance_rescale <= 1.0:
@@ -167,8 +196,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         raise NotImplementedError("run_inference(training_mode=True) with autograd enabled: use photoverse_amd.train.TrainStep(face_loss=..., vae=...) - "
                                   "the differentiated form of this call - or call under torch.no_grad() for the forward semantics of the mode")
     device = torch.device(device)
-    # infer.py:39-40 - the sampler is rebuilt from the loaded scheduler's config on every call
-    sch = DPMSolverMultistepScheduler.from_config(scheduler.config)
+    sch = _scheduler_for(scheduler, sampler)
     batch = example["pixel_values"].shape[0] if "pixel_values" in example else example["pixel_values_clip"].shape[0]
 
     uncond_input_ids = example.get("negative_text_input_ids", None)                      # :43-49
@@ -199,6 +227,8 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                 generator = torch.manual_seed(seed)
                 torch.randn(shape, generator=generator)
             hires_noise = torch.randn(shape2, generator=generator)      # the draw that follows the first one
+    if stochastic:                                    # after the start-noise draws: those are what they were
+        noise_seed = int(seed) if seed is not None else int(torch.randint(0, 1 << 62, (1,)).item())
 
     inpaint = inpaint_mask is not None
     start = strength_start(timesteps, float(strength))
@@ -239,16 +269,20 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     loop.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
     if inpaint:
         loop.set_inpaint(lat_mask.to(device), latents0, start_noise)
+    if stochastic:
+        loop.set_noise_stream(noise_seed, int(sample_offset), stream=0)
     loop.reset(noise, start)
     latents = loop.run().clone()
 
     if hires:
         # second pass: upscale + re-noise in one launch, then the tail of a fresh schedule at the large size under the same conditioning
-        sch2 = DPMSolverMultistepScheduler.from_config(scheduler.config)
+        sch2 = _scheduler_for(scheduler, sampler)
         x_start, start2 = hires_start(latents, hires_noise.to(device), sch2, hires_steps, hires_strength)
         loop2 = _loop_for(unet, batch, hires_latent_size, encoder_hidden_states_image.shape[1], hires_steps, guidance_scale, sch2,
                           fusion_seed=0 if seed is None else int(seed), **guide)
         loop2.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
+        if stochastic:
+            loop2.set_noise_stream(noise_seed, int(sample_offset), stream=1)
         loop2.reset(x_start, start2)
         latents = loop2.run().clone()
 

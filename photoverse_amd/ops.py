@@ -940,6 +940,23 @@ class Recorder:
         self._add(self.lib.pv_cfg_dpm_step_guided, _ptr(eps_u), _ptr(eps_i), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
                   float(g_text), float(g_text if g_image is None else g_image), float(rescale), _ptr(mask), _ptr(known), _ptr(noise), B, ch, hw)
 
+    def cfg_dpm_step_stochastic(self, eps_u, eps_i, eps_c, latents, x0_prev, coef, state, rng, g_text, g_image=None, rescale=0.0, mask=None, known=None,
+                                noise=None):
+        """``cfg_dpm_step_guided`` as the step of SDE-DPM-Solver++(2M) (``pv_cfg_dpm_step_stochastic``): adds ``cn * z`` (``cn`` = column 7 of the
+        coefficient row of an ``sde-dpmsolver++`` table) with ``z ~ N(0, I)`` generated in the kernel.  ``rng``: four int32 device words
+        {seed_lo, seed_hi, sample_offset, stream} (uint32 bit patterns); the other arguments as ``cfg_dpm_step_guided``."""
+        B, ch = latents.shape[0], latents.shape[1]
+        hw = latents.numel() // (B * ch)
+        eps = [t for t in (eps_u, eps_i, eps_c) if t is not None]
+        opt = [t for t in (mask, known, noise) if t is not None]
+        assert len(opt) in (0, 3), "mask, known and noise come together"
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in eps + opt + [latents, x0_prev])
+        assert all(t.shape == latents.shape for t in eps + [x0_prev] + opt[1:]) and (not opt or mask.numel() == B * hw), [t.shape for t in eps + opt]
+        assert rng.dtype == torch.int32 and rng.numel() == 4 and rng.is_contiguous(), "rng: four int32 words"
+        self.keep.extend(eps + opt + [latents, x0_prev, coef, state, rng])
+        self._add(self.lib.pv_cfg_dpm_step_stochastic, _ptr(eps_u), _ptr(eps_i), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
+                  _ptr(rng), float(g_text), float(g_text if g_image is None else g_image), float(rescale), _ptr(mask), _ptr(known), _ptr(noise), B, ch, hw)
+
     def composite_clamp(self, gen, orig, mask, lo, hi, out=None):
         """out = clamp(m * gen + (1 - m) * orig, lo, hi); gen / orig fp32 (B, C, H, W) contiguous, mask fp32 (B, 1, H, W); ``out`` may be ``gen``."""
         B, ch = gen.shape[0], gen.shape[1]

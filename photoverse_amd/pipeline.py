@@ -13,6 +13,7 @@ from __future__ import annotations
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from .ops import Recorder, require_cuda
@@ -32,7 +33,7 @@ class DenoiseLoop:
                  scheduler: Optional[DPMSolverMultistepScheduler] = None, n_text: int = 77, use_graph: bool = True,
                  two_streams: bool = True, batch_splits: int = 1, training_mode: bool = False, fusion_seed: int = 0,
                  merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False,
-                 image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0):
+                 image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0, stochastic: bool = False):
         """``training_mode``: the reference enables grad on the LAST denoising step only (infer.py:99), where every cross-attention
         layer of both forwards then draws its branch fusion (attention_processor.py:413-420).  Here the draw runs on the device inside
         the captured step (``pv_fusion_draw`` keyed on the step counter), so the same graph serves all steps.  This is the forward semantics
@@ -62,7 +63,17 @@ class DenoiseLoop:
         each (at equal scales the ``eps_m`` terms cancel and the launcher evaluates the two-term expression: the bits of the two-forward loop).  The third engine reads the ``text_u`` / ``ip_c`` buffers of the other two, so ``set_conditioning`` is unchanged.  In this mode the three
         forwards are three whole plans (``merge_lowres`` is off) on the main and two side streams - three parallel branches of the captured graph;
         ``share_prefix`` still applies (all three start from the one prefix plan).  Not with ``training_mode``.  ``inpaint`` goes through the same
-        launcher's mask arguments."""
+        launcher's mask arguments.
+
+        ``stochastic`` (beyond the reference; [EXT] diffusers' ``algorithm_type="sde-dpmsolver++"``, the "DPM++ 2M SDE" of the front ends): the
+        solver step adds ``cn * z`` with fresh ``z ~ N(0, I)`` at every step.  The flag has to agree with the scheduler, whose type decides the
+        coefficient table: ``stochastic=True`` needs a ``DPMSolverMultistepScheduler(algorithm_type="sde-dpmsolver++")``, a scheduler of that type
+        needs ``stochastic=True`` - a mismatch either way is a ``ValueError``, so neither a silent deterministic run nor a table without its noise
+        can happen.  The tail is then ``pv_cfg_dpm_step_stochastic`` + ``pv_step_advance`` - still two launches, ``launches_per_step`` unchanged,
+        the forwards untouched.  The noise is generated inside that launch from ``self.rng`` = {seed_lo, seed_hi, sample_offset, stream} and the
+        device-resident step counter (``set_noise_stream``; seed 0 until it is called), so the one captured graph serves every step, seed, start
+        row and batch offset.  Combines with ``inpaint`` (the noise is added before the blend; the kept region keeps its one static noise),
+        ``image_guidance_scale``, ``guidance_rescale`` and ``share_prefix``.  Not with ``training_mode``."""
         dev = unet.device
         if dev.type != "cuda":
             raise RuntimeError("DenoiseLoop needs the UNet on a HIP device (no CPU path)")
@@ -76,7 +87,17 @@ class DenoiseLoop:
         three = self.image_guidance is not None
         if three and training_mode:
             raise ValueError("image_guidance_scale does not combine with training_mode=True")
-        sch = scheduler if scheduler is not None else DPMSolverMultistepScheduler()
+        self.stochastic = bool(stochastic)
+        if self.stochastic and training_mode:
+            raise ValueError("stochastic=True does not combine with training_mode=True")
+        if scheduler is None:
+            sch = DPMSolverMultistepScheduler(algorithm_type="sde-dpmsolver++" if self.stochastic else "dpmsolver++")
+        else:
+            sch = scheduler
+            if bool(getattr(sch, "stochastic", False)) != self.stochastic:
+                raise ValueError(f"stochastic={self.stochastic} does not agree with the scheduler ({type(sch).__name__}, algorithm_type "
+                                 f"{getattr(sch, 'config', {}).get('algorithm_type')!r}): the stochastic loop needs "
+                                 "DPMSolverMultistepScheduler(algorithm_type='sde-dpmsolver++'), every other scheduler stochastic=False")
         sch.set_timesteps(num_steps)
         self.scheduler = sch
         cfg = unet.config
@@ -170,7 +191,12 @@ class DenoiseLoop:
             self.mask = torch.ones((batch, 1, latent_size, latent_size), dtype=f32, device=dev)
             self.known = torch.zeros_like(self.latents)
             self.noise = torch.zeros_like(self.latents)
-        if three or self.guidance_rescale > 0.0:
+        if self.stochastic:
+            self.rng = torch.zeros(4, dtype=torch.int32, device=dev)     # {seed_lo, seed_hi, sample_offset, stream} as uint32 bit patterns: set_noise_stream
+            blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
+            self.tail.cfg_dpm_step_stochastic(self.eps_u, self.eps_m, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.rng,
+                                              self.guidance, self.image_guidance, self.guidance_rescale, **blend)
+        elif three or self.guidance_rescale > 0.0:
             blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
             self.tail.cfg_dpm_step_guided(self.eps_u, self.eps_m, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
                                           self.image_guidance, self.guidance_rescale, **blend)
@@ -213,9 +239,22 @@ class DenoiseLoop:
             require_cuda(src, what)
             dst.copy_(src.to(torch.float32).expand(dst.shape))
 
+    def set_noise_stream(self, seed: int, sample_offset: int = 0, stream: int = 0):
+        """The noise of a ``stochastic`` loop: ``seed`` (taken modulo 2^64) is the Philox key, ``sample_offset`` the global index of this loop's first
+        sample (sample ``b`` draws what sample 0 draws at ``sample_offset + b``: a rank's shard of a batch gets the noise of the one-GPU run),
+        ``stream`` tells apart the loops of one generation (the two passes of a hires run).  Contents only: the captured graph stays valid."""
+        if not self.stochastic:
+            raise RuntimeError("DenoiseLoop.set_noise_stream(): the loop was built without stochastic=True")
+        seed = int(seed) % (1 << 64)
+        if not (0 <= int(sample_offset) < (1 << 32) and 0 <= int(stream) < (1 << 32)):
+            raise ValueError(f"sample_offset and stream must be in [0, 2^32), got {sample_offset}, {stream}")
+        words = np.array([seed & 0xFFFFFFFF, seed >> 32, int(sample_offset), int(stream)], dtype=np.uint32).view(np.int32)
+        self.rng.copy_(torch.from_numpy(words.copy()))
+
     def reset(self, noise: torch.Tensor, start: int = 0):
         """latents = noise * init_noise_sigma (``infer.py:70``); step counter to ``start`` (0: the whole schedule; > 0: the last ``T - start`` steps
-        of it, ``noise`` then being latents already at ``timesteps[start]``'s noise level)."""
+        of it, ``noise`` then being latents already at ``timesteps[start]``'s noise level).  The noise stream of a ``stochastic`` loop is not
+        touched: its draws are keyed on the absolute step, so the same stream gives the same run again."""
         start = int(start)
         if not 0 <= start < self.T:
             raise ValueError(f"DenoiseLoop.reset(): start {start} is outside the schedule of {self.T} steps")
@@ -378,6 +417,9 @@ class PhotoVersePipeline:
                     # the second pass's noise is the NEXT draw of that generator over the global batch, as in the seeded 1-GPU run
                     s2 = kw["hires_latent_size"]
                     kw["hires_noise"] = torch.randn((n, self.unet.config.in_channels, s2, s2), generator=generator)[sl]
+            # the stochastic sampler's per-step noise is keyed on the GLOBAL sample index: with ``seed`` sample i of the sharded run gets the noise of
+            # sample i of the 1-GPU run (unseeded, every rank draws a stream key of its own: the ranks' noises are unrelated, as their start noises are)
+            kw["sample_offset"] = sl.start
             out = run_inference(local, self.tokenizer, self.image_encoder, self.text_encoder, self.unet, self.text_adapter,
                                 self.image_adapter, self.vae, self.scheduler, self.device, list(image_encoder_layers_idx), **kw)
             return gather_latents(out, world, force=True)

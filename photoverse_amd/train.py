@@ -557,7 +557,9 @@ class TrainStep:
         h, w, seq = self.H, self.W, self.S_len
         main = self._snapshot()
         f = self.face = SimpleNamespace(ns=ns, weight=weight, guidance=guidance, T=T)
-        sch = DPMSolverMultistepScheduler.from_config(noise_scheduler.config) if noise_scheduler is not None else DPMSolverMultistepScheduler()
+        # the plan's last step is the deterministic pv_cfg_dpm_step whatever sampler the loaded config names (the stochastic one is inference only)
+        sch = (DPMSolverMultistepScheduler.from_config(noise_scheduler.config, algorithm_type="dpmsolver++") if noise_scheduler is not None
+               else DPMSolverMultistepScheduler())
         sch.set_timesteps(T)
         f.scheduler = sch
         coef_host = sch.coefficient_table()
