@@ -12,6 +12,10 @@ still comes from ``--input_image_path``), ``--strength`` (img2img: run only the 
 ``--image_guidance_scale`` (a guidance scale of its own for the identity - the image tokens - beside ``--guidance_scale`` for the prompt: a third
 forward per step) and ``--guidance_rescale`` (renormalise the guided prediction against the over-saturation of high scales);
 ``--sampler sde-dpmsolver++`` (the stochastic form of the solver, "DPM++ 2M SDE": fresh noise at every step, keyed on ``--seed``).
+
+``--pag_scale`` (perturbed-attention guidance: one more forward per step with the self-attention map of the ``--pag_layers`` transformers replaced by
+the identity, and the prediction pushed away from it - repairs eyes, teeth and symmetry at low ``--guidance_scale`` without raising it) and
+``--pag_layers`` (name prefixes of the UNet's transformers such as ``mid_block`` or ``up_blocks.1``, or ``all``; default the mid block).
 """
 import argparse
 import os
@@ -56,6 +60,10 @@ parser.add_argument("--guidance_rescale", type=float, default=0.0,
                     help="In [0, 1]: scale the guided noise prediction towards the conditional one's standard deviation (0 = off)")
 parser.add_argument("--sampler", choices=["dpmsolver++", "sde-dpmsolver++"], default="dpmsolver++",
                     help="dpmsolver++: deterministic DPM-Solver++(2M); sde-dpmsolver++: its stochastic form (fresh noise per step, drawn on the device)")
+parser.add_argument("--pag_scale", type=float, default=None,
+                    help="Perturbed-attention guidance scale (one more forward per step with identity self-attention maps in --pag_layers; default off)")
+parser.add_argument("--pag_layers", nargs="+", type=str, default=["mid_block"],
+                    help="Transformers whose self-attention is perturbed: name prefixes (mid_block, up_blocks.1, down_blocks.0.attentions.0, ...) or all")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -128,7 +136,7 @@ if __name__ == "__main__":
                             strength=args.strength, inpaint_mask=prepare_mask(args), paste_back=not args.no_paste_back,
                             hires_latent_size=args.hires_latent_size, hires_strength=args.hires_strength, hires_timesteps=args.hires_timesteps,
                             image_guidance_scale=args.image_guidance_scale, guidance_rescale=args.guidance_rescale,
-                            sampler=args.sampler)
+                            sampler=args.sampler, pag_scale=args.pag_scale, pag_layers=tuple(args.pag_layers))
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

@@ -512,6 +512,18 @@ int pv_cfg_dpm_step_stochastic(const float* eps_uncond, const float* eps_image, 
                                const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float rescale,
                                const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
                                void* stream);
+/* (ABI 19, a symbol added) pv_cfg_dpm_step_guided / _stochastic with one more prediction: [EXT] perturbed-attention guidance (Ahn et al. 2024;
+ * diffusers' pag_scale).  ep = eps of the conditional forward in which the self-attention map of the chosen layers is the identity:
+ *   e0 = the guided prediction of pv_cfg_dpm_step_guided (two or three forwards; g_image == g_text drops eps_image)
+ *   e  = e0 + g_pag*(ec - ep)
+ *   f  = rescale*std_b(ec)/std_b(e) + (1 - rescale)     on THAT e;   e = f*e
+ * then the solver update, with rng != NULL the cn*z of pv_cfg_dpm_step_stochastic (rng == NULL: the deterministic step), and the inpainting blend.
+ * eps_perturbed == NULL or g_pag == 0: eps_perturbed is not read and the launch is that of pv_cfg_dpm_step_guided (rng == NULL) /
+ * pv_cfg_dpm_step_stochastic (rng != NULL), bit for bit.  Every other argument and limit as pv_cfg_dpm_step_guided; g_pag finite. */
+int pv_cfg_dpm_step_pag(const float* eps_uncond, const float* eps_image, const float* eps_cond, const float* eps_perturbed, float* latents,
+                        float* x0_prev, const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float g_pag,
+                        float rescale, const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
+                        void* stream);
 
 /* Grad-mode branch fusion of PhotoVerseAttnProcessor2_0 (attention_processor.py:413-420) WITHOUT the reference's per-layer
  * host sync (`torch.rand(1).item()`): one tiny launch draws u ~ U(0,1) per cross-attention layer on the device

@@ -157,6 +157,8 @@ SIGNATURES = {
                                        c_void_p, c_int, c_int, c_int, c_void_p]),
     "pv_cfg_dpm_step_stochastic": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
                                            c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "pv_cfg_dpm_step_pag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
+                                    c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "pv_step_advance": (c_int, [c_void_p, c_void_p]),
     "pv_fusion_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p]),
     "pv_cast_f32_to_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
@@ -218,7 +220,7 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
-        except AttributeError:     # a library of the same ABI number built before the symbol was added (pv_cfg_dpm_step_guided / _stochastic came without a new number)
+        except AttributeError:     # a library of the same ABI number built before the symbol was added (pv_cfg_dpm_step_guided / _stochastic / _pag came without a new number)
             raise HipExtensionMissing(f"{LIB} has no symbol {name}: it is older than this package - rebuild it with `python -m photoverse_amd.build`") from None
         fn.restype = res
         fn.argtypes = args

@@ -267,18 +267,29 @@ __device__ __forceinline__ float pv_guided_eps(float u, float m, float c, float 
     return u + gt * (c - u);
 }
 
+// [EXT] Perturbed-attention guidance (Ahn et al. 2024) on top of the guided prediction: ep = eps of the conditional forward whose chosen self-attention
+// maps are the identity;  e = e0 + g_pag (ec - ep).  PAG = false is pv_guided_eps itself (ep is not read).
+template <bool IMG, bool PAG>
+__device__ __forceinline__ float pv_guided_eps_pag(float u, float m, float c, float p, float gt, float gi, float gp) {
+    const float e0 = pv_guided_eps<IMG>(u, m, c, gt, gi);
+    if (PAG) return e0 + gp * (c - p);
+    return e0;
+}
+
 // cfg_dpm_step_kernel / cfg_dpm_step_masked_kernel with the guided prediction above and [EXT] diffusers' guidance_rescale:
 //   f  = rescale * std_b(ec) / std_b(e) + (1 - rescale)      per sample b over its chw elements (f = 1 where std_b(e) == 0)
 //   e  = f * e;  x0, xn, the blend: the expressions of the two kernels above (IMG = RESCALE = NOISE = false reproduces their bits)
 // NOISE (pv_cfg_dpm_step_stochastic, the SDE form of the solver): xn += cn * z before the blend, cn = column 7 of the row, z the four normals of the
 // Philox block keyed (rng[0], rng[1]) at counter (float4 index inside the sample, rng[2] + sample, step index, rng[3]).  Everything z depends
 // on is contents of device buffers, so a captured launch serves any seed / start row / batch offset, and a replay gives the bits of an eager run.
+// PAG (pv_cfg_dpm_step_pag): e is pv_guided_eps_pag - the statistics of the rescale are those of that e; everything behind e is unchanged.
 // One workgroup per sample, so the statistics need no second launch and no scratch: mean first, then the squared deviations (noise
 // predictions are not zero-mean), both passes over eps_* only; the last pass recomputes e and writes latents / x0_prev in place.
-template <bool IMG, bool RESCALE, bool MASK, bool NOISE>
-__global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* eu, const float* em, const float* ec, float* lat, float* x0p,
-                                                                   const float* coef, const int32_t* state, const uint32_t* __restrict__ rng,
-                                                                   float gt, float gi, float rescale, const float* __restrict__ mask,
+template <bool IMG, bool RESCALE, bool MASK, bool NOISE, bool PAG>
+__global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* eu, const float* em, const float* ec, const float* ep, float* lat,
+                                                                   float* x0p, const float* coef, const int32_t* state,
+                                                                   const uint32_t* __restrict__ rng, float gt, float gi, float gp, float rescale,
+                                                                   const float* __restrict__ mask,
                                                                    const float* __restrict__ known, const float* __restrict__ noise, long chw,
                                                                    int hw) {
     __shared__ float red[4 * 16];
@@ -292,10 +303,11 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
             const float4_t u = *reinterpret_cast<const float4_t*>(eu + i);
             const float4_t cc = *reinterpret_cast<const float4_t*>(ec + i);
             const float4_t mm = IMG ? *reinterpret_cast<const float4_t*>(em + i) : u;
+            const float4_t pp = PAG ? *reinterpret_cast<const float4_t*>(ep + i) : cc;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 sc += cc[j];
-                se += pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi);
+                se += pv_guided_eps_pag<IMG, PAG>(u[j], mm[j], cc[j], pp[j], gt, gi, gp);
             }
         }
         pv_block_sum2(sc, se, red);
@@ -306,9 +318,10 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
             const float4_t u = *reinterpret_cast<const float4_t*>(eu + i);
             const float4_t cc = *reinterpret_cast<const float4_t*>(ec + i);
             const float4_t mm = IMG ? *reinterpret_cast<const float4_t*>(em + i) : u;
+            const float4_t pp = PAG ? *reinterpret_cast<const float4_t*>(ep + i) : cc;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float dc = cc[j] - mc, de = pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi) - me;
+                const float dc = cc[j] - mc, de = pv_guided_eps_pag<IMG, PAG>(u[j], mm[j], cc[j], pp[j], gt, gi, gp) - me;
                 qc += dc * dc;
                 qe += de * de;
             }
@@ -331,6 +344,7 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
         const float4_t u = *reinterpret_cast<const float4_t*>(eu + i);
         const float4_t cc = *reinterpret_cast<const float4_t*>(ec + i);
         const float4_t mm = IMG ? *reinterpret_cast<const float4_t*>(em + i) : u;
+        const float4_t pp = PAG ? *reinterpret_cast<const float4_t*>(ep + i) : cc;
         float4_t x = *reinterpret_cast<const float4_t*>(lat + i);
         float4_t xp = *reinterpret_cast<const float4_t*>(x0p + i);
         float4_t x0;
@@ -342,7 +356,7 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
             const float4_t nz = *reinterpret_cast<const float4_t*>(noise + i);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float e = pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi);
+                float e = pv_guided_eps_pag<IMG, PAG>(u[j], mm[j], cc[j], pp[j], gt, gi, gp);
                 if (RESCALE) e = f * e;
                 x0[j] = ca * x[j] + cb * e;
                 float xn = cx * x[j] + c0 * x0[j] + c1 * xp[j];
@@ -353,7 +367,7 @@ __global__ __launch_bounds__(1024) void cfg_dpm_step_guided_kernel(const float* 
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float e = pv_guided_eps<IMG>(u[j], mm[j], cc[j], gt, gi);
+                float e = pv_guided_eps_pag<IMG, PAG>(u[j], mm[j], cc[j], pp[j], gt, gi, gp);
                 if (RESCALE) e = f * e;
                 x0[j] = ca * x[j] + cb * e;
                 x[j] = cx * x[j] + c0 * x0[j] + c1 * xp[j];
@@ -825,58 +839,77 @@ extern "C" int pv_cfg_dpm_step_masked(const float* eps_uncond, const float* eps_
     return PV_CHECK_LAUNCH();
 }
 
-template <bool IMG, bool RESCALE, bool NOISE>
-static int launch_cfg_dpm_step_guided(const float* eu, const float* em, const float* ec, float* lat, float* x0p, const float* coef,
-                                      const int32_t* state, const uint32_t* rng, float gt, float gi, float rescale, const float* mask,
+template <bool IMG, bool RESCALE, bool NOISE, bool PAG = false>
+static int launch_cfg_dpm_step_guided(const float* eu, const float* em, const float* ec, const float* ep, float* lat, float* x0p, const float* coef,
+                                      const int32_t* state, const uint32_t* rng, float gt, float gi, float gp, float rescale, const float* mask,
                                       const float* known, const float* noise, int batch, long chw, int hw, hipStream_t stream) {
     const long nv = chw / 4;
     const dim3 grid((unsigned)batch), block((unsigned)(nv >= 1024 ? 1024 : (nv + 63) / 64 * 64));     // whole waves: every lane shuffles
     if (mask)
-        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, true, NOISE>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, rng,
-                           gt, gi, rescale, mask, known, noise, chw, hw);
+        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, true, NOISE, PAG>), grid, block, 0, stream, eu, em, ec, ep, lat, x0p, coef, state,
+                           rng, gt, gi, gp, rescale, mask, known, noise, chw, hw);
     else
-        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, false, NOISE>), grid, block, 0, stream, eu, em, ec, lat, x0p, coef, state, rng,
-                           gt, gi, rescale, mask, known, noise, chw, hw);
+        hipLaunchKernelGGL((cfg_dpm_step_guided_kernel<IMG, RESCALE, false, NOISE, PAG>), grid, block, 0, stream, eu, em, ec, ep, lat, x0p, coef, state,
+                           rng, gt, gi, gp, rescale, mask, known, noise, chw, hw);
     return PV_CHECK_LAUNCH();
 }
 
 // the body of pv_cfg_dpm_step_guided (rng == NULL) and pv_cfg_dpm_step_stochastic (rng != NULL): validation before the first HIP call
+// and of pv_cfg_dpm_step_pag (either, with eps_perturbed / g_pag; the other two pass nullptr / 0 and land on the PAG = false instantiations)
 template <bool NOISE>
-static int cfg_dpm_step_guided_entry(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
-                                     const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float rescale,
-                                     const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
+static int cfg_dpm_step_guided_entry(const float* eps_uncond, const float* eps_image, const float* eps_cond, const float* eps_perturbed, float* latents,
+                                     float* x0_prev, const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image,
+                                     float g_pag, float rescale, const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
                                      void* stream) {
     if (!eps_uncond || !eps_cond || !latents || !x0_prev || !coef || !state || (NOISE && !rng)) return (int)hipErrorInvalidValue;
     if (batch < 1 || channels < 1 || hw < 1 || (hw % 4)) return (int)hipErrorInvalidValue;
     if ((mask != nullptr) != (known != nullptr) || (mask != nullptr) != (noise != nullptr)) return (int)hipErrorInvalidValue;
-    if (!__builtin_isfinite(g_text) || !__builtin_isfinite(g_image) ||!(rescale >= 0.f && rescale <= 1.f)) return (int)hipErrorInvalidValue;
+    if (!__builtin_isfinite(g_text) || !__builtin_isfinite(g_image) || !__builtin_isfinite(g_pag) || !(rescale >= 0.f && rescale <= 1.f))
+        return (int)hipErrorInvalidValue;
     const int64_t chw = (int64_t)channels * hw, lim = (int64_t)1 << 31;
     if (chw >= lim || (int64_t)batch * chw >= lim) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
     // equal scales: the eps_image terms cancel, eu + g (em - eu) + g (ec - em) == eu + g (ec - eu).  Evaluate the two-term expression: the same
     // polynomial with fewer roundings, so a three-forward step at equal scales has the bits of the two-forward step (eps_image is then not read)
     if (eps_image && g_image == g_text) eps_image = nullptr;
-#define PV_GUIDED(IMG, RS) \
-    launch_cfg_dpm_step_guided<IMG, RS, NOISE>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, rng, g_text, g_image, rescale, mask, \
-                                               known, noise, batch, (long)chw, hw, s)
-    if (eps_image) return rescale > 0.f ? PV_GUIDED(true, true) : PV_GUIDED(true, false);
-    return rescale > 0.f ? PV_GUIDED(false, true) : PV_GUIDED(false, false);
+    // no perturbed prediction, or scale 0: the term vanishes - the instantiations (and bits) of the entry points without it; eps_perturbed is not read
+    if (eps_perturbed && g_pag == 0.f) eps_perturbed = nullptr;
+#define PV_GUIDED(IMG, RS, PAG) \
+    launch_cfg_dpm_step_guided<IMG, RS, NOISE, PAG>(eps_uncond, eps_image, eps_cond, eps_perturbed, latents, x0_prev, coef, state, rng, g_text, g_image, \
+                                                    g_pag, rescale, mask, known, noise, batch, (long)chw, hw, s)
+    if (eps_perturbed) {
+        if (eps_image) return rescale > 0.f ? PV_GUIDED(true, true, true) : PV_GUIDED(true, false, true);
+        return rescale > 0.f ? PV_GUIDED(false, true, true) : PV_GUIDED(false, false, true);
+    }
+    if (eps_image) return rescale > 0.f ? PV_GUIDED(true, true, false) : PV_GUIDED(true, false, false);
+    return rescale > 0.f ? PV_GUIDED(false, true, false) : PV_GUIDED(false, false, false);
 #undef PV_GUIDED
 }
 
 extern "C" int pv_cfg_dpm_step_guided(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
                                       const float* coef, const int32_t* state, float g_text, float g_image, float rescale, const float* mask,
                                       const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw, void* stream) {
-    return cfg_dpm_step_guided_entry<false>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, nullptr, g_text, g_image, rescale, mask,
-                                            known, noise, batch, channels, hw, stream);
+    return cfg_dpm_step_guided_entry<false>(eps_uncond, eps_image, eps_cond, nullptr, latents, x0_prev, coef, state, nullptr, g_text, g_image, 0.f, rescale,
+                                            mask, known, noise, batch, channels, hw, stream);
 }
 
 extern "C" int pv_cfg_dpm_step_stochastic(const float* eps_uncond, const float* eps_image, const float* eps_cond, float* latents, float* x0_prev,
                                           const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float rescale,
                                           const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
                                           void* stream) {
-    return cfg_dpm_step_guided_entry<true>(eps_uncond, eps_image, eps_cond, latents, x0_prev, coef, state, rng, g_text, g_image, rescale, mask,
+    return cfg_dpm_step_guided_entry<true>(eps_uncond, eps_image, eps_cond, nullptr, latents, x0_prev, coef, state, rng, g_text, g_image, 0.f, rescale, mask,
                                            known, noise, batch, channels, hw, stream);
+}
+
+extern "C" int pv_cfg_dpm_step_pag(const float* eps_uncond, const float* eps_image, const float* eps_cond, const float* eps_perturbed, float* latents,
+                                   float* x0_prev, const float* coef, const int32_t* state, const uint32_t* rng, float g_text, float g_image, float g_pag,
+                                   float rescale, const float* mask, const float* known, const float* noise, int32_t batch, int32_t channels, int32_t hw,
+                                   void* stream) {
+    if (rng)
+        return cfg_dpm_step_guided_entry<true>(eps_uncond, eps_image, eps_cond, eps_perturbed, latents, x0_prev, coef, state, rng, g_text, g_image, g_pag,
+                                               rescale, mask, known, noise, batch, channels, hw, stream);
+    return cfg_dpm_step_guided_entry<false>(eps_uncond, eps_image, eps_cond, eps_perturbed, latents, x0_prev, coef, state, nullptr, g_text, g_image, g_pag,
+                                            rescale, mask, known, noise, batch, channels, hw, stream);
 }
 
 extern "C" int pv_composite_clamp_f32(const float* gen, const float* orig, const float* mask, float* out, float lo, float hi, int32_t batch,

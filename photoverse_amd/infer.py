@@ -23,6 +23,10 @@ launch (``pv_cfg_dpm_step_guided``).
 And the sampler ([EXT] diffusers' ``algorithm_type="sde-dpmsolver++"``, the "DPM++ 2M SDE" of the front ends): ``sampler="sde-dpmsolver++"`` runs the
 stochastic form of the solver, whose fresh noise per step is generated inside the solver-step launch (``pv_cfg_dpm_step_stochastic``) from a Philox
 stream keyed on ``seed``, the global sample index and the device-resident step counter - the captured graph is the same for every step and seed.
+
+And perturbed-attention guidance ([EXT] Ahn et al. 2024; diffusers' ``pag_scale`` / ``pag_applied_layers``): ``pag_scale`` adds a forward per step whose
+chosen self-attention maps are the identity (``UNetEngine(perturb=...)``, started from the conditional forward's tensors at its first perturbed layer)
+and one term to the solver-step launch (``pv_cfg_dpm_step_pag``).
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ import torch
 
 from .pipeline import DenoiseLoop
 from .scheduler import DPMSolverMultistepScheduler
+from .unet import resolve_pag_layers
 
 
 #: captured loops kept per UNet (each holds two engines of static activations: ~4 GB at bs=16) - least recently used evicted
@@ -101,16 +106,17 @@ def _scheduler_for(scheduler, sampler) -> DPMSolverMultistepScheduler:
 
 
 def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False,
-              image_guidance=None, guidance_rescale=0.0) -> DenoiseLoop:
+              image_guidance=None, guidance_rescale=0.0, pag_scale=None, pag_layers=()) -> DenoiseLoop:
     cache = unet.__dict__.setdefault("_denoise_loops", OrderedDict())
     stochastic = bool(getattr(scheduler, "stochastic", False))      # the sampler: part of the key through the scheduler run_inference built for it
     key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed),
-           None if image_guidance is None else float(image_guidance), float(guidance_rescale), stochastic, bool(inpaint))
+           None if image_guidance is None else float(image_guidance), float(guidance_rescale), stochastic,
+           None if pag_scale is None else float(pag_scale), tuple(pag_layers), bool(inpaint))
     loop = cache.pop(key, None)
     if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0):
         loop = DenoiseLoop(unet, batch, latent_size, n_ip, steps, guidance, scheduler=scheduler, training_mode=training_mode,
                            fusion_seed=fusion_seed, inpaint=inpaint, image_guidance_scale=image_guidance, guidance_rescale=guidance_rescale,
-                           stochastic=stochastic)
+                           stochastic=stochastic, pag_scale=pag_scale, pag_layers=tuple(pag_layers) or ("mid_block",))
         loop.unet_version = unet.__dict__.get("_pack_version", 0)
     cache[key] = loop                               # most recently used last
     while len(cache) > MAX_CACHED_LOOPS:
@@ -121,8 +127,8 @@ def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, traini
 def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler,
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
-                  image_guidance_scale=None, guidance_rescale=0.0, sampler="dpmsolver++", sample_offset=0, inpaint_mask=None, paste_back=True,
-                  hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
+                  image_guidance_scale=None, guidance_rescale=0.0, sampler="dpmsolver++", sample_offset=0, pag_scale=None, pag_layers=("mid_block",),
+                  inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
     global batch once and hands each rank its slice.
@@ -151,7 +157,14 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     hires run from stream 1.  ``sample_offset`` (int >= 0): the global index of this call's first sample - sample ``b`` gets the per-step noise sample
     ``sample_offset + b`` of a whole-batch call gets (``PhotoVersePipeline(shard=True)`` passes the rank's offset).  That equivalence needs ``seed``:
     unseeded, every call - every rank of a sharded run - draws a key of its own.  The kept region of an
-    ``inpaint_mask`` run keeps its one static noise.  Not with ``training_mode``."""
+    ``inpaint_mask`` run keeps its one static noise.  Not with ``training_mode``.
+
+    ``pag_scale`` (None or 0: off) / ``pag_layers``: perturbed-attention guidance.  One more forward per step - the conditional one with the
+    self-attention map of the chosen transformers replaced by the identity - and the prediction is pushed away from it by
+    ``pag_scale * (eps_c - eps_p)``: broken structure (eyes, teeth, asymmetry) at the low guidance scales this model is driven at is repaired without
+    raising ``guidance_scale``.  ``pag_layers``: name prefixes of the UNet's transformers (``"mid_block"``, ``"up_blocks.1"``,
+    ``"down_blocks.0.attentions.0"``, ...) or ``"all"``; an entry that selects nothing is a ``ValueError``.  Holds for both passes of a hires run
+    and combines with every keyword above except ``training_mode``."""
     if sampler not in SAMPLERS:                                                             # before any model is touched
         raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     if not (isinstance(sample_offset, numbers.Integral) and not isinstance(sample_offset, bool) and 0 <= sample_offset < (1 << 32)):
@@ -167,7 +180,15 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         raise ValueError("image_guidance_scale / guidance_rescale do not combine with training_mode=True")
     if image_guidance_scale is not None and float(image_guidance_scale) == float(guidance_scale):
         image_guidance_scale = None                    # the ordinary formula: two forwards
-    guide = dict(image_guidance=image_guidance_scale, guidance_rescale=float(guidance_rescale))
+    if pag_scale is not None and not _is_finite_real(pag_scale):                            # still before any model is touched
+        raise ValueError(f"pag_scale must be a finite number or None, got {pag_scale!r}")
+    if pag_scale is not None and float(pag_scale) == 0.0:
+        pag_scale = None                               # off: the loop without it
+    if pag_scale is not None and training_mode:
+        raise ValueError("pag_scale does not combine with training_mode=True")
+    # the layers resolve against the UNet's module tree (names only; no weight, no launch): an unknown entry fails here, before any model runs
+    pag_names = resolve_pag_layers(unet, pag_layers) if pag_scale is not None else ()
+    guide = dict(image_guidance=image_guidance_scale, guidance_rescale=float(guidance_rescale), pag_scale=pag_scale, pag_layers=pag_names)
     hires = hires_latent_size is not None
     if hires:                                          # before anything else: the first pass must not run for a second one that cannot
         if not _is_positive_int(hires_latent_size):

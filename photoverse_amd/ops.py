@@ -957,6 +957,24 @@ class Recorder:
         self._add(self.lib.pv_cfg_dpm_step_stochastic, _ptr(eps_u), _ptr(eps_i), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
                   _ptr(rng), float(g_text), float(g_text if g_image is None else g_image), float(rescale), _ptr(mask), _ptr(known), _ptr(noise), B, ch, hw)
 
+    def cfg_dpm_step_pag(self, eps_u, eps_i, eps_c, eps_p, latents, x0_prev, coef, state, g_text, g_image=None, g_pag=0.0, rescale=0.0, rng=None,
+                         mask=None, known=None, noise=None):
+        """``cfg_dpm_step_guided`` (``rng`` None) / ``cfg_dpm_step_stochastic`` (``rng`` given) with perturbed-attention guidance
+        (``pv_cfg_dpm_step_pag``): ``eps_p`` = eps of the conditional forward with identity self-attention maps in the chosen layers; the prediction
+        gains ``g_pag * (eps_c - eps_p)`` before the rescale.  ``eps_p`` None or ``g_pag`` 0: the bits of the other two launchers."""
+        B, ch = latents.shape[0], latents.shape[1]
+        hw = latents.numel() // (B * ch)
+        eps = [t for t in (eps_u, eps_i, eps_c, eps_p) if t is not None]
+        opt = [t for t in (mask, known, noise) if t is not None]
+        assert len(opt) in (0, 3), "mask, known and noise come together"
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in eps + opt + [latents, x0_prev])
+        assert all(t.shape == latents.shape for t in eps + [x0_prev] + opt[1:]) and (not opt or mask.numel() == B * hw), [t.shape for t in eps + opt]
+        assert rng is None or (rng.dtype == torch.int32 and rng.numel() == 4 and rng.is_contiguous()), "rng: four int32 words"
+        self.keep.extend(eps + opt + [latents, x0_prev, coef, state] + ([rng] if rng is not None else []))
+        self._add(self.lib.pv_cfg_dpm_step_pag, _ptr(eps_u), _ptr(eps_i), _ptr(eps_c), _ptr(eps_p), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
+                  _ptr(rng), float(g_text), float(g_text if g_image is None else g_image), float(g_pag), float(rescale), _ptr(mask), _ptr(known),
+                  _ptr(noise), B, ch, hw)
+
     def composite_clamp(self, gen, orig, mask, lo, hi, out=None):
         """out = clamp(m * gen + (1 - m) * orig, lo, hi); gen / orig fp32 (B, C, H, W) contiguous, mask fp32 (B, 1, H, W); ``out`` may be ``gen``."""
         B, ch = gen.shape[0], gen.shape[1]

@@ -10,6 +10,7 @@ with no communication inside the loop; final latents are collected with ONE ``al
 """
 from __future__ import annotations
 
+import numbers
 import os
 from typing import Optional, Tuple
 
@@ -33,7 +34,8 @@ class DenoiseLoop:
                  scheduler: Optional[DPMSolverMultistepScheduler] = None, n_text: int = 77, use_graph: bool = True,
                  two_streams: bool = True, batch_splits: int = 1, training_mode: bool = False, fusion_seed: int = 0,
                  merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False,
-                 image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0, stochastic: bool = False):
+                 image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0, stochastic: bool = False,
+                 pag_scale: Optional[float] = None, pag_layers=("mid_block",), share_trunk: Optional[bool] = None):
         """``training_mode``: the reference enables grad on the LAST denoising step only (infer.py:99), where every cross-attention
         layer of both forwards then draws its branch fusion (attention_processor.py:413-420).  Here the draw runs on the device inside
         the captured step (``pv_fusion_draw`` keyed on the step counter), so the same graph serves all steps.  This is the forward semantics
@@ -73,7 +75,22 @@ class DenoiseLoop:
         the forwards untouched.  The noise is generated inside that launch from ``self.rng`` = {seed_lo, seed_hi, sample_offset, stream} and the
         device-resident step counter (``set_noise_stream``; seed 0 until it is called), so the one captured graph serves every step, seed, start
         row and batch offset.  Combines with ``inpaint`` (the noise is added before the blend; the kept region keeps its one static noise),
-        ``image_guidance_scale``, ``guidance_rescale`` and ``share_prefix``.  Not with ``training_mode``."""
+        ``image_guidance_scale``, ``guidance_rescale`` and ``share_prefix``.  Not with ``training_mode``.
+
+        ``pag_scale`` / ``pag_layers`` (beyond the reference; [EXT] perturbed-attention guidance, Ahn et al. 2024, diffusers' ``pag_scale`` /
+        ``pag_applied_layers``).  None or 0 builds the loop described above: same engines, same tail launcher, same ``launches_per_step``.  Otherwise
+        one more forward runs per step - the conditional one with the self-attention map of the transformers ``resolve_pag_layers(unet, pag_layers)``
+        selects replaced by the identity (``UNetEngine(perturb=...)`` -> ``eps_p``) - and the prediction gains ``pag_scale * (eps_c - eps_p)``
+        before the rescale: structure is repaired without a higher guidance scale.  The perturbed engines (``engines_p_attn``, one per batch split)
+        read ``text_c`` / ``ip_c``, so ``set_conditioning`` is unchanged; they run on the conditional forward's stream right after it - no additional
+        stream or graph branch.  ``merge_lowres`` is off in this mode, ``share_prefix`` still applies.  The tail is ``pv_cfg_dpm_step_pag`` +
+        ``pv_step_advance``.  Combines with ``image_guidance_scale`` (four forwards), ``guidance_rescale``, ``inpaint`` and ``stochastic``.  Not with
+        ``training_mode``.
+
+        ``share_trunk`` (None: on whenever PAG is on): up to its first perturbed transformer the perturbed forward IS the conditional forward, so
+        its plan adopts the conditional plan's activation and skip tensors there (``UNetEngine(trunk=...)``) and records only the rest - with the
+        default layer, the mid block, the whole down path.  Same kernels on the same inputs: the bits of ``share_trunk=False``, which records the
+        whole perturbed forward."""
         dev = unet.device
         if dev.type != "cuda":
             raise RuntimeError("DenoiseLoop needs the UNet on a HIP device (no CPU path)")
@@ -87,6 +104,15 @@ class DenoiseLoop:
         three = self.image_guidance is not None
         if three and training_mode:
             raise ValueError("image_guidance_scale does not combine with training_mode=True")
+        if pag_scale is not None and not (isinstance(pag_scale, numbers.Real) and not isinstance(pag_scale, bool) and np.isfinite(float(pag_scale))):
+            raise ValueError(f"pag_scale must be a finite number or None, got {pag_scale!r}")
+        self.pag_scale = 0.0 if pag_scale is None else float(pag_scale)
+        pag = self.pag_scale != 0.0
+        if pag and training_mode:
+            raise ValueError("pag_scale does not combine with training_mode=True")
+        from .unet import resolve_pag_layers
+        self.pag_layers = resolve_pag_layers(unet, pag_layers) if pag else ()
+        self.share_trunk = bool(pag and (share_trunk is None or share_trunk))
         self.stochastic = bool(stochastic)
         if self.stochastic and training_mode:
             raise ValueError("stochastic=True does not combine with training_mode=True")
@@ -125,7 +151,8 @@ class DenoiseLoop:
         self.eps_u = torch.empty_like(self.latents)
         self.eps_c = torch.empty_like(self.latents)
         self.eps_m = torch.empty_like(self.latents) if three else None      # eps(uncond text, cond image tokens)
-        self.engines_u, self.engines_c, self.engines_m, self.engines_p, self.engines_i = [], [], [], [], []
+        self.eps_p = torch.empty_like(self.latents) if pag else None        # eps(cond) with perturbed self-attention
+        self.engines_u, self.engines_c, self.engines_m, self.engines_p, self.engines_i, self.engines_p_attn = [], [], [], [], [], []
         if share_prefix is None:
             share_prefix = os.environ.get("PV_SHARE_PREFIX", "0") == "1"
         first = unet.down_blocks[0]
@@ -145,7 +172,7 @@ class DenoiseLoop:
             rows = 2 * batch * (latent_size >> split) ** 2
             # (... and at the launch-bound end, up to 1024 rows - bs = 1 / 2 at 64 x 64 latents - the merged plan's fewer launches win again: +1.0 % / +0.4 %)
             merge_lowres = (env != "0") if env is not None else (rows >= _MERGE_MIN_ROWS or rows <= 1024)
-        self.merge_lowres = bool(merge_lowres and not training_mode and not three and batch_splits == 1 and n_lv > split
+        self.merge_lowres = bool(merge_lowres and not training_mode and not three and not pag and batch_splits == 1 and n_lv > split
                                  and ((latent_size >> split) ** 2) % 64 == 0 and latent_size % (1 << (n_lv - 1)) == 0)
         if self.merge_lowres:
             # text / image-token buffers of the two branches are the halves of ONE buffer: the merged plan reads it whole
@@ -185,6 +212,15 @@ class DenoiseLoop:
             if three:
                 self.engines_i.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_u[i * sb * n_text:(i + 1) * sb * n_text],
                                                   ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_m[sl], **kw))
+            if pag:
+                kwp = dict(kw)
+                if self.share_trunk:
+                    kwp.update(trunk=self.engines_c[i])             # starts from the conditional plan's tensors (the prefix, if any, lies inside them)
+                elif "down_blocks.0.attentions.0" in self.pag_layers:
+                    kwp.pop("prefix", None)                         # the prefix holds that transformer's UNperturbed attn1
+                self.engines_p_attn.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_c[i * sb * n_text:(i + 1) * sb * n_text],
+                                                       ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_p[sl], perturb=self.pag_layers,
+                                                       **kwp))
         self.eng_u, self.eng_c = self.engines_u[0], self.engines_c[0]
         self.tail = Recorder(dev)
         if self.inpaint:
@@ -193,6 +229,11 @@ class DenoiseLoop:
             self.noise = torch.zeros_like(self.latents)
         if self.stochastic:
             self.rng = torch.zeros(4, dtype=torch.int32, device=dev)     # {seed_lo, seed_hi, sample_offset, stream} as uint32 bit patterns: set_noise_stream
+        if pag:
+            blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
+            self.tail.cfg_dpm_step_pag(self.eps_u, self.eps_m, self.eps_c, self.eps_p, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
+                                       self.image_guidance, self.pag_scale, self.guidance_rescale, rng=self.rng if self.stochastic else None, **blend)
+        elif self.stochastic:
             blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
             self.tail.cfg_dpm_step_stochastic(self.eps_u, self.eps_m, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.rng,
                                               self.guidance, self.image_guidance, self.guidance_rescale, **blend)
@@ -216,8 +257,8 @@ class DenoiseLoop:
     @property
     def all_engines(self):
         """Every plan of a step (uncond / cond branches, with ``merge_lowres`` the merged low-resolution part, with ``image_guidance_scale`` the
-        image-only branch)."""
-        return self.engines_u + self.engines_c + self.engines_m + self.engines_p + self.engines_i
+        image-only branch, with ``pag_scale`` the perturbed branch)."""
+        return self.engines_u + self.engines_c + self.engines_m + self.engines_p + self.engines_i + self.engines_p_attn
 
     # ------------------------------------------------------------------
     def set_conditioning(self, cond: Tuple[torch.Tensor, torch.Tensor], uncond: Tuple[torch.Tensor, torch.Tensor]):
@@ -302,17 +343,29 @@ class DenoiseLoop:
             # overlap the others'; joined before the combine
             main = torch.cuda.current_stream()
             engines = self.engines_u + self.engines_c + self.engines_i
+            after = self._after_cond()
             for side, eng in zip(self._sides, engines[1:]):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     eng.rec.run()
+                    if id(eng) in after:                # the perturbed forward: same stream, right behind its conditional forward
+                        after[id(eng)].rec.run()
             engines[0].rec.run()
+            if id(engines[0]) in after:
+                after[id(engines[0])].rec.run()
             for side in self._sides:
                 main.wait_stream(side)
         else:
+            after = self._after_cond()
             for e in self.engines_u + self.engines_c + self.engines_i:
                 e.rec.run()
+                if id(e) in after:
+                    after[id(e)].rec.run()
         self.tail.run()
+
+    def _after_cond(self):
+        """conditional engine -> the perturbed engine that follows it on its stream (``pag_scale``; empty otherwise)"""
+        return {id(c): p for c, p in zip(self.engines_c, self.engines_p_attn)}
 
     def capture(self):
         """Capture one step into a HIP graph.  The capture itself does not execute the step."""

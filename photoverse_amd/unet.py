@@ -188,6 +188,43 @@ def _conv1_w(w: torch.Tensor) -> torch.Tensor:
     return w.detach().reshape(w.shape[0], -1).to(torch.float16).contiguous()
 
 
+def transformer_names(unet) -> Tuple[str, ...]:
+    """The transformers of ``unet`` under the names ``UNetEngine._transformer`` receives, in execution order (down path, mid block, up path)."""
+    names = [f"down_blocks.{bi}.attentions.{i}" for bi, blk in enumerate(unet.down_blocks) if blk.has_attn for i in range(len(blk.attentions))]
+    names += [f"mid_block.attentions.{i}" for i in range(len(unet.mid_block.attentions))]
+    names += [f"up_blocks.{bi}.attentions.{i}" for bi, blk in enumerate(unet.up_blocks) if blk.has_attn for i in range(len(blk.attentions))]
+    return tuple(names)
+
+
+def resolve_pag_layers(unet, layers=("mid_block",)) -> Tuple[str, ...]:
+    """The transformers whose self-attention perturbed-attention guidance perturbs ([EXT] diffusers' ``pag_applied_layers``): every entry of
+    ``layers`` selects the transformers whose name starts with it; ``"all"`` (the string, or as an entry) selects every one.  Returned in execution
+    order, each once.  An entry that selects nothing, or no entry at all, is a ``ValueError``.  Host-side: reads the module tree only."""
+    names = transformer_names(unet)
+    if isinstance(layers, str):
+        layers = (layers,)
+    try:
+        layers = tuple(layers)
+    except TypeError:
+        raise ValueError(f"pag_layers must be a string or a sequence of strings, got {layers!r}") from None
+    if not layers or not all(isinstance(e, str) and e for e in layers):
+        raise ValueError(f"pag_layers must be non-empty strings, got {layers!r}")
+    chosen = set()
+    for e in layers:
+        hit = names if e == "all" else [nm for nm in names if nm.startswith(e)]
+        if not hit:
+            raise ValueError(f"pag_layers entry {e!r} selects no transformer of this UNet (there are: {', '.join(names)})")
+        chosen.update(hit)
+    return tuple(nm for nm in names if nm in chosen)
+
+
+def fold_identity_attention(attn: Attention) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Self-attention with the identity attention map is ``to_out(to_v(x))`` and ``to_v`` has no bias: ONE Linear with
+    ``W = to_out.weight @ to_v.weight`` (product in fp32, rounded to fp16 once) and ``to_out``'s bias (fp32)."""
+    w = (attn.to_out[0].weight.detach().float() @ attn.to_v.weight.detach().float()).to(torch.float16).contiguous()
+    return w, _f32(attn.to_out[0].bias)
+
+
 class UNetEngine:
     """Static launch plan of one UNet forward for a fixed (batch, height, width, ip tokens, timestep rows)."""
 
@@ -196,7 +233,7 @@ class UNetEngine:
                  latents_in: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None,
                  ip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, device_fusion: Optional[str] = None,
                  fusion_seed: int = 0, segment: Optional[str] = None, split: int = 2, mid_in=None, mid_out=None, big_min: Optional[int] = None,
-                 prefix=None):
+                 prefix=None, perturb=(), trunk: Optional["UNetEngine"] = None):
         """``device_fusion``: None - branch weights (w_text, w_ip) are launch parameters patched by the host (``_set_fusion``);
         ``"always"`` - every forward draws them on the device (grad-mode semantics of attention_processor.py:413-420, graph-safe);
         ``"last_step"`` - drawn only when the loop state says this is the last denoising step (``run_inference(training_mode=True)``,
@@ -212,7 +249,18 @@ class UNetEngine:
         first ResnetBlock and the first transformer block up to its self-attention - is the same computation in the uncond and cond forwards of a
         CFG step (same latents, same timestep).  ``segment="prefix"`` records it once (``self.prefix_out``: conv_in's output, the ResnetBlock's
         output, the hidden states behind attn1, with the column statistics their GroupNorm consumers need); a plan given ``prefix=`` that
-        dictionary starts from those tensors instead of recomputing them.  Exact: the same kernels on the same inputs."""
+        dictionary starts from those tensors instead of recomputing them.  Exact: the same kernels on the same inputs.
+
+        ``perturb`` (perturbed-attention guidance, DenoiseLoop(pag_scale=...)): transformer names as ``_transformer`` receives them
+        (``resolve_pag_layers``).  In those the self-attention map is the identity - every query returns its own value row - so attn1 is
+        ``hs + to_out(to_v(norm1(hs)))``: one LayerNorm and ONE Linear with the two weights folded at plan build, no q, no k, no attention launch.
+        ``perturb=()`` records exactly the plan described above.
+
+        ``trunk`` (with ``perturb``): the whole plan of the CONDITIONAL forward of the same step (same latents, timestep, conditioning buffers).  Up
+        to its first perturbed transformer a perturbed forward is that forward, so this plan adopts the other's activation and skip tensors at the
+        entry of that transformer (``trunk.trunk_points``, with their column statistics) and records only what follows; it must run after ``trunk``
+        on the same stream.  Exact for the same reason as the prefix.  Recorder tensors are never reused inside a plan, so what the conditional
+        plan wrote is still there.  The conditioning-only launches (``rec_cond``) and the time embedding stay this plan's own."""
         self.unet, self.B, self.H, self.W, self.P, self.NT = unet, batch, h, w, n_ip, n_text
         if segment not in (None, "outer", "mid", "prefix"):
             raise ValueError("segment must be None, 'outer', 'mid' or 'prefix'")
@@ -220,7 +268,20 @@ class UNetEngine:
             raise ValueError("a plan segment needs the shared mid_in / mid_out buffers (and host-side fusion weights)")
         if (segment == "prefix" or prefix is not None) and (device_fusion is not None or segment == "mid"):
             raise ValueError("the shared prefix exists for the inference plans of the two CFG branches")
-        self.prefix_in, self.prefix_out = prefix, None
+        self.perturb = tuple(perturb)
+        if (self.perturb or trunk is not None) and (segment is not None or device_fusion is not None):
+            raise ValueError("perturbed self-attention exists for whole inference plans (no segment, host-side fusion weights)")
+        if trunk is not None and not self.perturb:
+            raise ValueError("trunk= needs perturb=: an unperturbed plan IS the conditional plan")
+        if trunk is not None and (trunk.segment is not None or trunk.perturb or (trunk.B, trunk.H, trunk.W) != (batch, h, w)):
+            raise ValueError("trunk must be the whole unperturbed plan of the same shape")
+        if prefix is not None and "down_blocks.0.attentions.0" in self.perturb and trunk is None:
+            raise ValueError("the shared prefix holds the unperturbed attn1 of down_blocks.0.attentions.0: build this plan without prefix=")
+        self.trunk = trunk
+        #: transformer name -> (x, its column statistics, [(skip, statistics, h, w), ...]) at the entry of that transformer (whole plans only): what a
+        #: perturbed plan given ``trunk=`` this engine starts from.  References only - no launch depends on it.
+        self.trunk_points: Dict[str, tuple] = {}
+        self.prefix_in, self.prefix_out = (None if trunk is not None else prefix), None
         self.segment, self.split, self.mid_in, self.mid_out = segment, split, mid_in, mid_out
         cfg = unet.config
         rec = self.rec = Recorder(device)
@@ -315,8 +376,19 @@ class UNetEngine:
         else:
             g = rec.groupnorm(x, _f32(m.norm.weight), _f32(m.norm.bias), batch=b, hw=n, eps=m.norm.eps, act=ACT_NONE)
             hs = rec.gemm(g, _conv1_w(m.proj_in.weight), bias=_f32(m.proj_in.bias), rows_per_image=n)
-        # --- attn1 (stock AttnProcessor2_0, models/unet.py:20-24) ---
         a1 = blk.attn1
+        if name in self.perturb:
+            # --- attn1 with the identity attention map: hs + to_out(to_v(norm1(hs))); to_v has no bias, so the two Linears are one ---
+            assert not stop_after_attn1
+            wf, bf = fold_identity_attention(a1)
+            if Recorder.gemm_ln_supported(b * n, C, C, False, rec.big_min):
+                wl, bl = Recorder.fold_layernorm(wf, bf, _f32(blk.norm1.weight), _f32(blk.norm1.bias))
+                hs = rec.gemm(hs, wl, bias=bl, residual=hs, rows_per_image=n, ln_gamma=True, ln_eps=blk.norm1.eps, splitk=0)
+            else:
+                n1 = rec.layernorm(hs, _f32(blk.norm1.weight), _f32(blk.norm1.bias), eps=blk.norm1.eps)
+                hs = rec.gemm(n1, wf, bias=bf, residual=hs, rows_per_image=n)
+            return self._transformer_tail(name, m, x, hs, b, h, w)
+        # --- attn1 (stock AttnProcessor2_0, models/unet.py:20-24) ---
         wqkv = torch.cat([_f16(a1.to_q.weight), _f16(a1.to_k.weight), _f16(a1.to_v.weight)], 0).contiguous()
         if USE_ROWGEMM and Recorder.row_gemm_supported(C, 3 * C):
             # norm1 + [to_q; to_k; to_v] as ONE row-owning launch (pv_rowgemm.hip): rows normalised in registers, weights streamed
@@ -436,11 +508,38 @@ class UNetEngine:
                 self.rec.colstats.pop(key, None)
             return t
 
+        # perturbed plan on a shared trunk: nothing is recorded (x is None, the skips are placeholders) until the first perturbed transformer, in
+        # execution order, whose entry state is adopted from the conditional plan
+        skipping = self.trunk is not None
+        trunk_at = next((nm for nm in transformer_names(u) if nm in self.perturb), None)
+        unknown = [nm for nm in self.perturb if nm not in transformer_names(u)]
+        if unknown:
+            raise ValueError(f"perturb names no transformer of this UNet: {unknown}")
+
+        def cs_of(t):
+            return self.rec.colstats.get((t.data_ptr(), t.shape[0], t.shape[1]))
+
+        def xf(name, m, x, h, w, **kw):
+            nonlocal skipping
+            if skipping and name == trunk_at:
+                tx, tskips = self.trunk.trunk_points[name]
+                assert [(sh, sw) for _, _, sh, sw in tskips] == [(sh, sw) for _, sh, sw in skips]
+                x = adopt(tx, B * h * w)
+                skips[:] = [(adopt((t, cs), B * sh * sw), sh, sw) for t, cs, sh, sw in tskips]
+                skipping = False
+            elif seg is None and not self.perturb:
+                self.trunk_points[name] = ((x, cs_of(x)), [(t, cs_of(t), sh, sw) for t, sh, sw in skips])
+            if skipping:
+                return None
+            return self._transformer(name, m, x, B, h, w, **kw)
+
         pre = self.prefix_in
         first = u.down_blocks[0]
         if (seg == "prefix" or pre is not None) and not (first.has_attn and len(first.resnets) >= 1):
             raise ValueError("the shared prefix needs an attention down block first (conv_in -> ResnetBlock -> transformer block)")
-        if pre is not None:
+        if skipping:
+            x, skips = None, [(None, h, w)]
+        elif pre is not None:
             # conv_in, the first ResnetBlock and the first transformer block up to attn1 were recorded by the prefix plan
             x = adopt(pre["conv_in"], B * h * w)
             skips = [(x, h, w)]
@@ -471,27 +570,28 @@ class UNetEngine:
             for i, res in enumerate(blk.resnets):
                 if pre is not None and bi == 0 and i == 0:
                     x = adopt(pre["res"], B * h * w)
-                    x = self._transformer("down_blocks.0.attentions.0", blk.attentions[0], x, B, h, w, resume_hs=pre["hs"])
+                    x = xf("down_blocks.0.attentions.0", blk.attentions[0], x, h, w, resume_hs=pre["hs"])
                     skips.append((x, h, w))
                     continue
-                x = self._resnet(res, x, None, B, h, w, temb_all, toffs[id(res)])
+                x = None if skipping else self._resnet(res, x, None, B, h, w, temb_all, toffs[id(res)])
                 if blk.has_attn:
-                    x = self._transformer(f"down_blocks.{bi}.attentions.{i}", blk.attentions[i], x, B, h, w)
+                    x = xf(f"down_blocks.{bi}.attentions.{i}", blk.attentions[i], x, h, w)
                 skips.append((x, h, w))
             if blk.downsamplers is not None:
                 conv = blk.downsamplers[0].conv
                 boundary = seg == "outer" and bi == split - 1         # this branch's half of the merged part's input
-                x = rec.gemm(x, _conv3_w(conv.weight), bias=_f32(conv.bias),
-                             conv=dict(batch=B, hin=h, win=w, hout=h // 2, wout=w // 2, stride=2), colstats=True,
-                             out=self.mid_in[0] if boundary else None, colstats_out=self.mid_in[1] if boundary else None)
+                if not skipping:
+                    x = rec.gemm(x, _conv3_w(conv.weight), bias=_f32(conv.bias),
+                                 conv=dict(batch=B, hin=h, win=w, hout=h // 2, wout=w // 2, stride=2), colstats=True,
+                                 out=self.mid_in[0] if boundary else None, colstats_out=self.mid_in[1] if boundary else None)
                 h, w = h // 2, w // 2
                 if not boundary:
                     skips.append((x, h, w))                           # (at the boundary the skip belongs to the merged part)
         if seg != "outer":
             mb = u.mid_block
-            x = self._resnet(mb.resnets[0], x, None, B, h, w, temb_all, toffs[id(mb.resnets[0])])
-            x = self._transformer("mid_block.attentions.0", mb.attentions[0], x, B, h, w)
-            x = self._resnet(mb.resnets[1], x, None, B, h, w, temb_all, toffs[id(mb.resnets[1])])
+            x = None if skipping else self._resnet(mb.resnets[0], x, None, B, h, w, temb_all, toffs[id(mb.resnets[0])])
+            x = xf("mid_block.attentions.0", mb.attentions[0], x, h, w)
+            x = None if skipping else self._resnet(mb.resnets[1], x, None, B, h, w, temb_all, toffs[id(mb.resnets[1])])
         n_up = len(u.up_blocks)
         for bi, blk in enumerate(u.up_blocks):
             outer_up = bi >= n_up - split
@@ -504,17 +604,18 @@ class UNetEngine:
             for i, res in enumerate(blk.resnets):
                 sk, sh, sw = skips.pop()
                 assert (sh, sw) == (h, w)
-                x = self._resnet(res, x, sk, B, h, w, temb_all, toffs[id(res)])   # channel concat [x | skip] is never materialised
+                x = None if skipping else self._resnet(res, x, sk, B, h, w, temb_all, toffs[id(res)])   # channel concat [x | skip] is never materialised
                 if blk.has_attn:
-                    x = self._transformer(f"up_blocks.{bi}.attentions.{i}", blk.attentions[i], x, B, h, w)
+                    x = xf(f"up_blocks.{bi}.attentions.{i}", blk.attentions[i], x, h, w)
             if blk.upsamplers is not None:
                 conv = blk.upsamplers[0].conv
                 boundary = seg == "mid" and bi == n_up - split - 1
-                x = rec.gemm(x, _conv3_w(conv.weight), bias=_f32(conv.bias),
-                             conv=dict(batch=B, hin=h, win=w, hout=h * 2, wout=w * 2, upsample=1), colstats=True,
-                             out=self.mid_out[0] if boundary else None, colstats_out=self.mid_out[1] if boundary else None)
+                if not skipping:
+                    x = rec.gemm(x, _conv3_w(conv.weight), bias=_f32(conv.bias),
+                                 conv=dict(batch=B, hin=h, win=w, hout=h * 2, wout=w * 2, upsample=1), colstats=True,
+                                 out=self.mid_out[0] if boundary else None, colstats_out=self.mid_out[1] if boundary else None)
                 h, w = h * 2, w * 2
-        assert not skips, "every skip connection is consumed inside the plan segment that produced it"
+        assert not skipping and not skips, "every skip connection is consumed inside the plan segment that produced it"
         if seg == "mid":
             self.out = x
             return
