@@ -16,6 +16,9 @@ forward per step) and ``--guidance_rescale`` (renormalise the guided prediction 
 ``--pag_scale`` (perturbed-attention guidance: one more forward per step with the self-attention map of the ``--pag_layers`` transformers replaced by
 the identity, and the prediction pushed away from it - repairs eyes, teeth and symmetry at low ``--guidance_scale`` without raising it) and
 ``--pag_layers`` (name prefixes of the UNet's transformers such as ``mid_block`` or ``up_blocks.1``, or ``all``; default the mid block).
+
+``--freeu B1 B2 S1 S2`` (FreeU: in the first two decoder blocks the first half of the backbone's channels is scaled by ``B1`` / ``B2`` and the skip
+connection's lowest frequencies by ``S1`` / ``S2``; the authors' values for SD-1.5 are ``1.5 1.6 0.9 0.2``; no additional forward).
 """
 import argparse
 import os
@@ -64,6 +67,8 @@ parser.add_argument("--pag_scale", type=float, default=None,
                     help="Perturbed-attention guidance scale (one more forward per step with identity self-attention maps in --pag_layers; default off)")
 parser.add_argument("--pag_layers", nargs="+", type=str, default=["mid_block"],
                     help="Transformers whose self-attention is perturbed: name prefixes (mid_block, up_blocks.1, down_blocks.0.attentions.0, ...) or all")
+parser.add_argument("--freeu", nargs=4, type=float, default=None, metavar=("B1", "B2", "S1", "S2"),
+                    help="FreeU: backbone scales B1 B2 and skip low-frequency scales S1 S2 of the first two decoder blocks (SD-1.5: 1.5 1.6 0.9 0.2; default off)")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -136,7 +141,8 @@ if __name__ == "__main__":
                             strength=args.strength, inpaint_mask=prepare_mask(args), paste_back=not args.no_paste_back,
                             hires_latent_size=args.hires_latent_size, hires_strength=args.hires_strength, hires_timesteps=args.hires_timesteps,
                             image_guidance_scale=args.image_guidance_scale, guidance_rescale=args.guidance_rescale,
-                            sampler=args.sampler, pag_scale=args.pag_scale, pag_layers=tuple(args.pag_layers))
+                            sampler=args.sampler, pag_scale=args.pag_scale, pag_layers=tuple(args.pag_layers),
+                            freeu=None if args.freeu is None else tuple(args.freeu))
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

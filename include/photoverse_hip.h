@@ -577,6 +577,20 @@ int pv_affine_rows_f32(const float* x, const float* y, const float* ca, const fl
  * upscale), x_start = sqrt(acp[t]) * upsample(latents) + sqrt(1 - acp[t]) * noise, in one launch. */
 int pv_resize_bilinear_affine_f32(const float* x, const float* y, const float* ca, const float* cb, float* out,
                                   int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t oh, int32_t ow, void* stream);
+/* (ABI 19, a symbol added) [EXT] FreeU (Si et al., CVPR 2024; diffusers' enable_freeu) on the two inputs of one decoder ResnetBlock, before their
+ * (virtual) channel concat, in ONE launch.  Rows are fp16 [batch*h*w][C]; image i is the h*w consecutive rows from i*h*w, row y*w + x its pixel (y, x).
+ *   backbone:  x_out[r][c] = fp16(float(x[r][c]) * (c < cx/2 ? b : 1))                                   (the upper half is copied bit for bit)
+ *   skip:      per (image, channel) plane p[y][x], diffusers' fourier_filter(threshold = 1, scale = s) - fftn, fftshift, the 2 x 2 window
+ *              [h/2-1 : h/2+1, w/2-1 : w/2+1] times s, ifftshift, ifftn, .real - in closed form: the window holds the frequencies (u, v) in {0, -1}^2,
+ *                X[u,v]          = sum_{y,x} p[y][x] * exp(-2 pi i (u y/h + v x/w))
+ *                skip_out[y][x]  = fp16(p[y][x] + (s - 1)/(h w) * sum_{u,v} Re(X[u,v] * exp(+2 pi i (u y/h + v x/w))))
+ *              seven real sums per plane and a rank-4 update; fp32 accumulation in a fixed order (no atomics: the same bits on every launch).
+ * Either half may be absent (x == x_out == NULL, or skip == skip_out == NULL; its widths and scale are then ignored) but not both; an input without
+ * its output (or the reverse) is rejected.  Inputs are read only, outputs must not be the inputs.  cx % 16 == 0, cs % 8 == 0, every row stride a
+ * multiple of 8 elements and >= its width, every pointer 16-byte aligned, h >= 2, w >= 2, batch >= 1, b and s finite, every extent
+ * (batch*h*w rows of ld elements) below 2 GiB. */
+int pv_freeu_rows(const void* x, int32_t ldx, int32_t cx, void* x_out, int32_t ldxo, float b, const void* skip, int32_t lds, int32_t cs,
+                  void* skip_out, int32_t ldso, float s, int32_t batch, int32_t h, int32_t w, void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

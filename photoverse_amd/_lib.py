@@ -168,6 +168,8 @@ SIGNATURES = {
     "pv_pointwise_nchw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "pv_affine_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "pv_resize_bilinear_affine_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "pv_freeu_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int,
+                              c_void_p]),
     "pv_posterior_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "pv_reduce_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "pv_clamp_f32": (c_int, [c_void_p, c_float, c_float, c_int64, c_void_p]),
@@ -220,7 +222,7 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
-        except AttributeError:     # a library of the same ABI number built before the symbol was added (pv_cfg_dpm_step_guided / _stochastic / _pag came without a new number)
+        except AttributeError:     # a library of the same ABI number built before the symbol was added (pv_cfg_dpm_step_guided / _stochastic / _pag and pv_freeu_rows came without a new number)
             raise HipExtensionMissing(f"{LIB} has no symbol {name}: it is older than this package - rebuild it with `python -m photoverse_amd.build`") from None
         fn.restype = res
         fn.argtypes = args

@@ -738,6 +738,141 @@ extern "C" int pv_resize_bilinear_affine_f32(const float* x, const float* y, con
     return PV_CHECK_LAUNCH();
 }
 
+namespace {
+// FreeU on the two inputs of one decoder ResnetBlock (header: pv_freeu_rows).  256 threads = 16 channel chunks of 8 (a thread's 16-byte load; the
+// 16 chunks of a row are 256 contiguous bytes) x 16 pixel lanes.
+// Blocks [0, skip_blocks): one (image, 128-channel group) of the skip each.  Pass 1: every thread walks the pixels lane, lane + 16, ... of its
+// chunk and accumulates the seven sums S0, sum p cos/sin(c), sum p cos/sin(a), sum p cos/sin(a + c)  (a = 2 pi y/h, c = 2 pi x/w) in fp32; the 16
+// lanes' partials meet in LDS and are added in lane order.  Pass 2 reads the same pixels again (the plane is at most a few hundred KB: L2) and
+// stores  p + k (S0 + Cc cos c + Sc sin c + Ca cos a + Sa sin a + Cac cos(a + c) + Sac sin(a + c)),  k = (s - 1)/(h w):  with
+// X[0,-1] = Cc + i Sc, X[-1,0] = Ca + i Sa, X[-1,-1] = Cac + i Sac that is the header's sum of Re(X[u,v] exp(+2 pi i (u y/h + v x/w))).
+// Every sum depends on the plane alone - not on the batch, the grid or the other half - so a plane has the same bits in every launch that holds it.
+// Blocks from skip_blocks on: the backbone half, one chunk per thread.
+constexpr int FREEU_CHUNKS = 16, FREEU_LANES = 16, FREEU_COLS = FREEU_CHUNKS * 8;
+
+__device__ __forceinline__ void freeu_trig(int p, int w, float inv_h, float inv_w, float (&t)[6]) {
+    const int y = p / w, x = p - y * w;
+    float sa, ca, sc, cc;
+    sincospif(2.f * (float)y * inv_h, &sa, &ca);          // y < h: the argument is below 2; y = h/2 gives exactly (0, -1)
+    sincospif(2.f * (float)x * inv_w, &sc, &cc);
+    t[0] = cc; t[1] = sc; t[2] = ca; t[3] = sa;
+    t[4] = ca * cc - sa * sc;                             // cos(a + c)
+    t[5] = sa * cc + ca * sc;                             // sin(a + c)
+}
+
+__global__ __launch_bounds__(256) void freeu_rows_kernel(const half_t* __restrict__ x, int ldx, int cx, half_t* __restrict__ xo, int ldxo, float b,
+                                                         long x_chunks, const half_t* __restrict__ sk, int lds, int cs, half_t* __restrict__ so,
+                                                         int ldso, float s, int h, int w, int groups, int skip_blocks) {
+    __shared__ __attribute__((aligned(16))) float part[2][FREEU_LANES][FREEU_COLS];     // 16 KB: one sum's partials, double buffered
+    __shared__ __attribute__((aligned(16))) float tot[7][FREEU_COLS];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= skip_blocks) {
+        const long i = (long)((int)blockIdx.x - skip_blocks) * 256 + tid;
+        if (i >= x_chunks) return;
+        const int cpr = cx >> 3;
+        const long r = i / cpr;
+        const int c0 = (int)(i - r * cpr) * 8;
+        half8_t v = *reinterpret_cast<const half8_t*>(x + r * ldx + c0);
+        if (c0 < (cx >> 1)) {                             // cx % 16 == 0: a chunk lies in one half
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] * b);
+        }
+        *reinterpret_cast<half8_t*>(xo + r * ldxo + c0) = v;
+        return;
+    }
+    const int img = (int)blockIdx.x / groups, grp = (int)blockIdx.x - img * groups;
+    const int chunk = tid & (FREEU_CHUNKS - 1), lane = tid >> 4;
+    const int c0 = grp * FREEU_COLS + chunk * 8;
+    const bool active = c0 < cs;                          // cs % 8 == 0: a chunk is whole or absent
+    const int hw = h * w;
+    const float inv_h = 1.f / (float)h, inv_w = 1.f / (float)w;
+    const half_t* src = sk + (long)img * hw * lds + c0;
+    float acc[7][8];
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[k][e] = 0.f;
+    if (active) {
+        for (int p = lane; p < hw; p += FREEU_LANES) {
+            const half8_t v = *reinterpret_cast<const half8_t*>(src + (long)p * lds);
+            float t[6];
+            freeu_trig(p, w, inv_h, inv_w, t);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float f = (float)v[e];
+                acc[0][e] += f;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) acc[k + 1][e] = fmaf(f, t[k], acc[k + 1][e]);
+            }
+        }
+    }
+    const float scale = (s - 1.f) / (float)hw;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        // sum k on buffer k & 1: the reads of a buffer (two sums back) lie before the barrier of the sum in between
+        *reinterpret_cast<float4_t*>(&part[k & 1][lane][chunk * 8]) = float4_t{acc[k][0], acc[k][1], acc[k][2], acc[k][3]};
+        *reinterpret_cast<float4_t*>(&part[k & 1][lane][chunk * 8 + 4]) = float4_t{acc[k][4], acc[k][5], acc[k][6], acc[k][7]};
+        __syncthreads();
+        if (tid < FREEU_COLS) {
+            float sum = 0.f;
+#pragma unroll
+            for (int l = 0; l < FREEU_LANES; ++l) sum += part[k & 1][l][tid];      // lane order: fixed
+            tot[k][tid] = sum * scale;
+        }
+    }
+    __syncthreads();
+    if (!active) return;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const float4_t lo = *reinterpret_cast<const float4_t*>(&tot[k][chunk * 8]), hi = *reinterpret_cast<const float4_t*>(&tot[k][chunk * 8 + 4]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { acc[k][e] = lo[e]; acc[k][e + 4] = hi[e]; }
+    }
+    half_t* dst = so + (long)img * hw * ldso + c0;
+    for (int p = lane; p < hw; p += FREEU_LANES) {
+        const half8_t v = *reinterpret_cast<const half8_t*>(src + (long)p * lds);
+        float t[6];
+        freeu_trig(p, w, inv_h, inv_w, t);
+        half8_t o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float d = acc[0][e];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) d = fmaf(acc[k + 1][e], t[k], d);
+            o[e] = (half_t)((float)v[e] + d);
+        }
+        *reinterpret_cast<half8_t*>(dst + (long)p * ldso) = o;
+    }
+}
+}  // namespace
+
+extern "C" int pv_freeu_rows(const void* x, int32_t ldx, int32_t cx, void* x_out, int32_t ldxo, float b, const void* skip, int32_t lds, int32_t cs,
+                             void* skip_out, int32_t ldso, float s, int32_t batch, int32_t h, int32_t w, void* stream) {
+    const bool do_x = x != nullptr || x_out != nullptr, do_s = skip != nullptr || skip_out != nullptr;
+    if (!do_x && !do_s) return (int)hipErrorInvalidValue;
+    if (batch < 1 || h < 2 || w < 2) return (int)hipErrorInvalidValue;
+    // rows of ld elements below 2 GiB = 2^30 halfs, checked factor by factor (the full product may not fit 64 bits)
+    const int64_t lim = (int64_t)1 << 30;
+    const int64_t rows = (int64_t)batch * h;
+    if (rows >= lim || rows * w >= lim) return (int)hipErrorInvalidValue;
+    auto bad_half = [&](const void* in, const void* out, int32_t ldi, int32_t ldo, int32_t c, int32_t cmod, float scale) {
+        return !in || !out || in == out || c <= 0 || (c % cmod) || ldi < c || ldo < c || (ldi % 8) || (ldo % 8) ||
+               (reinterpret_cast<uintptr_t>(in) % 16) || (reinterpret_cast<uintptr_t>(out) % 16) || !__builtin_isfinite(scale) ||
+               rows * w * ldi >= lim || rows * w * ldo >= lim;
+    };
+    if (do_x && bad_half(x, x_out, ldx, ldxo, cx, 16, b)) return (int)hipErrorInvalidValue;
+    if (do_s && bad_half(skip, skip_out, lds, ldso, cs, 8, s)) return (int)hipErrorInvalidValue;
+    const int groups = do_s ? (cs + FREEU_COLS - 1) / FREEU_COLS : 1;
+    const int64_t skip_blocks = do_s ? (int64_t)batch * groups : 0;
+    const int64_t x_chunks = do_x ? rows * w * (cx / 8) : 0;
+    const int64_t blocks = skip_blocks + (x_chunks + 255) / 256;
+    if (blocks >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(freeu_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const half_t*>(x), ldx, cx,
+                       reinterpret_cast<half_t*>(x_out), ldxo, b, (long)x_chunks, reinterpret_cast<const half_t*>(skip), lds, cs,
+                       reinterpret_cast<half_t*>(skip_out), ldso, s, h, w, groups, (int)skip_blocks);
+    return PV_CHECK_LAUNCH();
+}
+
 extern "C" int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream) {
     if (!moments || !eps || !out || batch <= 0 || chw <= 0) return (int)hipErrorInvalidValue;
     const long n = (long)batch * chw;

@@ -27,6 +27,10 @@ stream keyed on ``seed``, the global sample index and the device-resident step c
 And perturbed-attention guidance ([EXT] Ahn et al. 2024; diffusers' ``pag_scale`` / ``pag_applied_layers``): ``pag_scale`` adds a forward per step whose
 chosen self-attention maps are the identity (``UNetEngine(perturb=...)``, started from the conditional forward's tensors at its first perturbed layer)
 and one term to the solver-step launch (``pv_cfg_dpm_step_pag``).
+
+And FreeU ([EXT] Si et al., CVPR 2024; diffusers' ``enable_freeu``): ``freeu=(b1, b2, s1, s2)`` re-weights the decoder's first two up blocks inside every
+forward - the first half of the backbone's channels times ``b``, the four lowest spatial frequencies of the skip connection times ``s`` - with one
+launch per ResnetBlock (``pv_freeu_rows``: the Fourier filter in closed form, no FFT) and no further forward or weights.
 """
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ import torch
 
 from .pipeline import DenoiseLoop
 from .scheduler import DPMSolverMultistepScheduler
-from .unet import resolve_pag_layers
+from .unet import normalize_freeu, resolve_pag_layers
 
 
 #: captured loops kept per UNet (each holds two engines of static activations: ~4 GB at bs=16) - least recently used evicted
@@ -106,17 +110,17 @@ def _scheduler_for(scheduler, sampler) -> DPMSolverMultistepScheduler:
 
 
 def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False,
-              image_guidance=None, guidance_rescale=0.0, pag_scale=None, pag_layers=()) -> DenoiseLoop:
+              image_guidance=None, guidance_rescale=0.0, pag_scale=None, pag_layers=(), freeu=None) -> DenoiseLoop:
     cache = unet.__dict__.setdefault("_denoise_loops", OrderedDict())
     stochastic = bool(getattr(scheduler, "stochastic", False))      # the sampler: part of the key through the scheduler run_inference built for it
     key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed),
            None if image_guidance is None else float(image_guidance), float(guidance_rescale), stochastic,
-           None if pag_scale is None else float(pag_scale), tuple(pag_layers), bool(inpaint))
+           None if pag_scale is None else float(pag_scale), tuple(pag_layers), freeu, bool(inpaint))
     loop = cache.pop(key, None)
     if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0):
         loop = DenoiseLoop(unet, batch, latent_size, n_ip, steps, guidance, scheduler=scheduler, training_mode=training_mode,
                            fusion_seed=fusion_seed, inpaint=inpaint, image_guidance_scale=image_guidance, guidance_rescale=guidance_rescale,
-                           stochastic=stochastic, pag_scale=pag_scale, pag_layers=tuple(pag_layers) or ("mid_block",))
+                           stochastic=stochastic, pag_scale=pag_scale, pag_layers=tuple(pag_layers) or ("mid_block",), freeu=freeu)
         loop.unet_version = unet.__dict__.get("_pack_version", 0)
     cache[key] = loop                               # most recently used last
     while len(cache) > MAX_CACHED_LOOPS:
@@ -128,7 +132,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
                   image_guidance_scale=None, guidance_rescale=0.0, sampler="dpmsolver++", sample_offset=0, pag_scale=None, pag_layers=("mid_block",),
-                  inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
+                  freeu=None, inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
     global batch once and hands each rank its slice.
@@ -164,8 +168,17 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     ``pag_scale * (eps_c - eps_p)``: broken structure (eyes, teeth, asymmetry) at the low guidance scales this model is driven at is repaired without
     raising ``guidance_scale``.  ``pag_layers``: name prefixes of the UNet's transformers (``"mid_block"``, ``"up_blocks.1"``,
     ``"down_blocks.0.attentions.0"``, ...) or ``"all"``; an entry that selects nothing is a ``ValueError``.  Holds for both passes of a hires run
-    and combines with every keyword above except ``training_mode``."""
-    if sampler not in SAMPLERS:                                                             # before any model is touched
+    and combines with every keyword above except ``training_mode``.
+
+    ``freeu`` (None: off): FreeU as ``(b1, b2, s1, s2)`` or a mapping with exactly those keys, four finite numbers (the authors' SD-1.5 values:
+    ``(1.5, 1.6, 0.9, 0.2)``).  In the first two up blocks of every forward the first half of the backbone's channels is scaled by ``b1`` / ``b2`` and the
+    skip connection's four lowest spatial frequencies by ``s1`` / ``s2``: more weight on the semantics, less high-frequency detail from the skips, at no
+    additional forward.  ``(1, 1, 1, 1)`` is None: the plain call on the plain cached loop.  Holds for both passes of a hires run and combines with
+    every keyword above except ``training_mode``."""
+    freeu = normalize_freeu(freeu)                                                          # before any model is touched
+    if freeu is not None and training_mode:
+        raise ValueError("freeu does not combine with training_mode=True")
+    if sampler not in SAMPLERS:
         raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     if not (isinstance(sample_offset, numbers.Integral) and not isinstance(sample_offset, bool) and 0 <= sample_offset < (1 << 32)):
         raise ValueError(f"sample_offset must be an int in [0, 2^32), got {sample_offset!r}")
@@ -188,7 +201,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         raise ValueError("pag_scale does not combine with training_mode=True")
     # the layers resolve against the UNet's module tree (names only; no weight, no launch): an unknown entry fails here, before any model runs
     pag_names = resolve_pag_layers(unet, pag_layers) if pag_scale is not None else ()
-    guide = dict(image_guidance=image_guidance_scale, guidance_rescale=float(guidance_rescale), pag_scale=pag_scale, pag_layers=pag_names)
+    guide = dict(image_guidance=image_guidance_scale, guidance_rescale=float(guidance_rescale), pag_scale=pag_scale, pag_layers=pag_names, freeu=freeu)
     hires = hires_latent_size is not None
     if hires:                                          # before anything else: the first pass must not run for a second one that cannot
         if not _is_positive_int(hires_latent_size):

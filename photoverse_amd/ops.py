@@ -821,6 +821,30 @@ class Recorder:
         self._add(self.lib.pv_resize_bilinear_affine_f32, _ptr(x), _ptr(y), _ptr(ca), _ptr(cb), _ptr(out), B, ch, h, w, oh, ow)
         return out
 
+    def freeu(self, x, skip, *, batch: int, h: int, w: int, b: float, s: float):
+        """[EXT] FreeU on the two inputs of one decoder ResnetBlock -> ``(x', skip')``: ``x'`` = ``x`` with its first ``C // 2`` columns times ``b``, ``skip'`` =
+        ``skip`` with the four lowest frequencies (u, v) in {0, -1}^2 of every (image, channel) plane times ``s`` (``pv_freeu_rows``: both halves in ONE
+        launch, out of place).  ``x`` / ``skip``: fp16 row views [batch * h * w][C].  A half whose scale is exactly 1 is not launched and its input itself is
+        returned; with both at 1 nothing is recorded.  The outputs carry no column statistics: ``groupnorm`` runs its own statistics pass over them."""
+        b, s = float(b), float(s)
+        rows = batch * h * w
+        assert x.shape[0] == rows and skip.shape[0] == rows and x.dtype == torch.float16 and skip.dtype == torch.float16, (x.shape, skip.shape, rows)
+        xo = self.empty((rows, x.shape[1])) if b != 1.0 else None
+        so = self.empty((rows, skip.shape[1])) if s != 1.0 else None
+        if xo is None and so is None:
+            return x, skip
+        for t in (xo, so):
+            if t is not None:
+                self.colstats.pop((t.data_ptr(), rows, t.shape[1]), None)        # a fresh buffer: nothing stale may describe it
+        xin, sin = (x if xo is not None else None), (skip if so is not None else None)
+        ldx, cx = _rows(x) if xin is not None else (0, 0)
+        lds, cs = _rows(skip) if sin is not None else (0, 0)
+        self.keep.extend(t for t in (xin, sin) if t is not None)
+        # per skip element 6 FMAs + 1 add in either pass; bytes: every half read once and written once (the skip's second read comes from L2)
+        self._add(self.lib.pv_freeu_rows, _ptr(xin), ldx, cx, _ptr(xo), cx, b, _ptr(sin), lds, cs, _ptr(so), cs, s, batch, h, w,
+                  tag=("freeu_rows_kernel", 26.0 * rows * cs + 0.5 * rows * cx, 2.0 * 2 * rows * (cx + cs)))
+        return (xo if xo is not None else x), (so if so is not None else skip)
+
     def posterior_sample(self, moments, eps, out=None):
         """moments fp32 [B, 2c, h, w] (mean | logvar), eps fp32 [B, c, h, w] -> mean + exp(0.5 clamp(logvar)) eps."""
         B, c2 = moments.shape[0], moments.shape[1]

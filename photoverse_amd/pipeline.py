@@ -35,7 +35,7 @@ class DenoiseLoop:
                  two_streams: bool = True, batch_splits: int = 1, training_mode: bool = False, fusion_seed: int = 0,
                  merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False,
                  image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0, stochastic: bool = False,
-                 pag_scale: Optional[float] = None, pag_layers=("mid_block",), share_trunk: Optional[bool] = None):
+                 pag_scale: Optional[float] = None, pag_layers=("mid_block",), share_trunk: Optional[bool] = None, freeu=None):
         """``training_mode``: the reference enables grad on the LAST denoising step only (infer.py:99), where every cross-attention
         layer of both forwards then draws its branch fusion (attention_processor.py:413-420).  Here the draw runs on the device inside
         the captured step (``pv_fusion_draw`` keyed on the step counter), so the same graph serves all steps.  This is the forward semantics
@@ -90,7 +90,17 @@ class DenoiseLoop:
         ``share_trunk`` (None: on whenever PAG is on): up to its first perturbed transformer the perturbed forward IS the conditional forward, so
         its plan adopts the conditional plan's activation and skip tensors there (``UNetEngine(trunk=...)``) and records only the rest - with the
         default layer, the mid block, the whole down path.  Same kernels on the same inputs: the bits of ``share_trunk=False``, which records the
-        whole perturbed forward."""
+        whole perturbed forward.
+
+        ``freeu`` (beyond the reference; [EXT] FreeU, Si et al. 2024, diffusers' ``enable_freeu``): None, ``(b1, b2, s1, s2)`` or a mapping with those
+        keys (``unet.normalize_freeu``; all ones is None).  Every engine of the step is built with it (``UNetEngine(freeu=...)``) - uncond, cond,
+        image-only, merged low-resolution part, prefix, perturbed: all forwards of a step see the same UNet - and records one ``pv_freeu_rows`` launch
+        per ResnetBlock of the first two up blocks.  No further forward, stream or buffer; the tail is untouched.  None builds the loop described
+        above, launch for launch.  Combines with every mode above except ``training_mode``."""
+        from .unet import normalize_freeu
+        self.freeu = normalize_freeu(freeu)                  # host-side, before the UNet is touched
+        if self.freeu is not None and training_mode:
+            raise ValueError("freeu does not combine with training_mode=True")
         dev = unet.device
         if dev.type != "cuda":
             raise RuntimeError("DenoiseLoop needs the UNet on a HIP device (no CPU path)")
@@ -160,7 +170,7 @@ class DenoiseLoop:
         pre_kw = {}
         if self.share_prefix:
             self.engines_p.append(unet.engine(batch, latent_size, latent_size, n_ip, 1, latents_in=self.latents, segment="prefix", timesteps=self.timesteps,
-                                              state=self.state, n_text=n_text))
+                                              state=self.state, n_text=n_text, freeu=self.freeu))
             pre_kw = dict(prefix=self.engines_p[0].prefix_out)
         n_lv = len(cfg.block_out_channels)
         split = int(os.environ.get("PV_MERGE_SPLIT", "2"))     # resolution levels that stay in the per-branch plans (A/B switch; 3 = only 8 x 8 + mid merged)
@@ -187,7 +197,7 @@ class DenoiseLoop:
             mid_in_cs = torch.zeros((2 * batch * n_in // 64, 2, c_in), dtype=f32, device=dev)
             mid_out = torch.empty((2 * batch * n_out, c_out), dtype=f16, device=dev)
             mid_out_cs = torch.zeros((2 * batch * n_out // 64, 2, c_out), dtype=f32, device=dev)
-            kw = dict(timesteps=self.timesteps, state=self.state, n_text=n_text, split=split)
+            kw = dict(timesteps=self.timesteps, state=self.state, n_text=n_text, split=split, freeu=self.freeu)
             side_by_side = dict(big_min=_SIDE_BIG_MIN) if two_streams else {}      # heads / tails of the two branches run concurrently: half the chip each
             for i, (text, ip, eps, lst) in enumerate(((self.text_u, self.ip_u, self.eps_u, self.engines_u), (self.text_c, self.ip_c, self.eps_c, self.engines_c))):
                 half_in = (mid_in[i * batch * n_in:(i + 1) * batch * n_in], mid_in_cs[i * batch * n_in // 64:(i + 1) * batch * n_in // 64])
@@ -198,7 +208,7 @@ class DenoiseLoop:
                                               mid_in=(mid_in, mid_in_cs), mid_out=(mid_out, mid_out_cs), **kw))
         for i in range(0 if self.merge_lowres else batch_splits):
             sl = slice(i * sb, (i + 1) * sb)
-            kw = dict(timesteps=self.timesteps, state=self.state, latents_in=self.latents[sl], n_text=n_text, **pre_kw)
+            kw = dict(timesteps=self.timesteps, state=self.state, latents_in=self.latents[sl], n_text=n_text, freeu=self.freeu, **pre_kw)
             if two_streams and batch_splits == 1:
                 kw.update(big_min=_SIDE_BIG_MIN)                    # the two whole forwards run side by side
             if training_mode:

@@ -218,6 +218,29 @@ def resolve_pag_layers(unet, layers=("mid_block",)) -> Tuple[str, ...]:
     return tuple(nm for nm in names if nm in chosen)
 
 
+FREEU_KEYS = ("b1", "b2", "s1", "s2")
+
+
+def normalize_freeu(freeu) -> Optional[Tuple[float, float, float, float]]:
+    """The FreeU setting ([EXT] diffusers' ``enable_freeu(s1, s2, b1, b2)``) as ``(b1, b2, s1, s2)`` floats, or None for off: None, a sequence of four
+    finite reals in that order, or a mapping with exactly those four keys.  ``(1, 1, 1, 1)`` is off.  Anything else is a ``ValueError``.  Host-side."""
+    if freeu is None:
+        return None
+    import math
+    import numbers
+    from collections.abc import Mapping, Sequence
+    vals = None
+    if isinstance(freeu, Mapping):
+        if set(freeu.keys()) == set(FREEU_KEYS):
+            vals = [freeu[k] for k in FREEU_KEYS]
+    elif isinstance(freeu, Sequence) and not isinstance(freeu, (str, bytes)) and len(freeu) == 4:
+        vals = list(freeu)
+    if vals is None or not all(isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v) for v in vals):
+        raise ValueError(f"freeu must be None, four finite numbers (b1, b2, s1, s2) or a mapping with exactly the keys {FREEU_KEYS}, got {freeu!r}")
+    vals = tuple(float(v) for v in vals)
+    return None if vals == (1.0, 1.0, 1.0, 1.0) else vals
+
+
 def fold_identity_attention(attn: Attention) -> Tuple[torch.Tensor, torch.Tensor]:
     """Self-attention with the identity attention map is ``to_out(to_v(x))`` and ``to_v`` has no bias: ONE Linear with
     ``W = to_out.weight @ to_v.weight`` (product in fp32, rounded to fp16 once) and ``to_out``'s bias (fp32)."""
@@ -233,7 +256,7 @@ class UNetEngine:
                  latents_in: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None,
                  ip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, device_fusion: Optional[str] = None,
                  fusion_seed: int = 0, segment: Optional[str] = None, split: int = 2, mid_in=None, mid_out=None, big_min: Optional[int] = None,
-                 prefix=None, perturb=(), trunk: Optional["UNetEngine"] = None):
+                 prefix=None, perturb=(), trunk: Optional["UNetEngine"] = None, freeu=None):
         """``device_fusion``: None - branch weights (w_text, w_ip) are launch parameters patched by the host (``_set_fusion``);
         ``"always"`` - every forward draws them on the device (grad-mode semantics of attention_processor.py:413-420, graph-safe);
         ``"last_step"`` - drawn only when the loop state says this is the last denoising step (``run_inference(training_mode=True)``,
@@ -260,7 +283,16 @@ class UNetEngine:
         to its first perturbed transformer a perturbed forward is that forward, so this plan adopts the other's activation and skip tensors at the
         entry of that transformer (``trunk.trunk_points``, with their column statistics) and records only what follows; it must run after ``trunk``
         on the same stream.  Exact for the same reason as the prefix.  Recorder tensors are never reused inside a plan, so what the conditional
-        plan wrote is still there.  The conditioning-only launches (``rec_cond``) and the time embedding stay this plan's own."""
+        plan wrote is still there.  The conditioning-only launches (``rec_cond``) and the time embedding stay this plan's own.
+
+        ``freeu`` ([EXT] FreeU, Si et al. 2024; diffusers' ``enable_freeu``): None, or ``(b1, b2, s1, s2)`` (``normalize_freeu``).  In the first two up
+        blocks every ResnetBlock's inputs go through ``Recorder.freeu`` right where the skip is popped: the first half of the backbone's channels times
+        ``b``, the skip's four lowest spatial frequencies times ``s`` - one launch per ResnetBlock, out of place, so a perturbed plan that adopts this plan's
+        skips (``trunk=``) finds them raw and filters them itself.  Every plan kind that records those blocks has the hook (whole, ``"mid"`` at batch 2B,
+        ``"outer"`` tail, prefix-fed, ``trunk=``).  None records exactly the plan described above."""
+        self.freeu = normalize_freeu(freeu)
+        if self.freeu is not None and len(unet.up_blocks) < 2:
+            raise ValueError("freeu acts on the first two up blocks: this UNet has fewer")
         self.unet, self.B, self.H, self.W, self.P, self.NT = unet, batch, h, w, n_ip, n_text
         if segment not in (None, "outer", "mid", "prefix"):
             raise ValueError("segment must be None, 'outer', 'mid' or 'prefix'")
@@ -604,6 +636,8 @@ class UNetEngine:
             for i, res in enumerate(blk.resnets):
                 sk, sh, sw = skips.pop()
                 assert (sh, sw) == (h, w)
+                if self.freeu is not None and bi < 2 and not skipping:
+                    x, sk = rec.freeu(x, sk, batch=B, h=h, w=w, b=self.freeu[bi], s=self.freeu[2 + bi])
                 x = None if skipping else self._resnet(res, x, sk, B, h, w, temb_all, toffs[id(res)])   # channel concat [x | skip] is never materialised
                 if blk.has_attn:
                     x = xf(f"up_blocks.{bi}.attentions.{i}", blk.attentions[i], x, h, w)
