@@ -22,6 +22,13 @@ convolution is nine shifted matmuls.  Error bounds (every constant derived here,
   an activation with.
 * ``GELU_APPROX = 1.25e-5``: the documented absolute error bound of the epilogues' erf approximation, per unit |x| (``pv_common.h``).
 
+* fp32 pointwise launchers (the solver steps, the resize, the embeds): every operation rounds within U32 of its own result; a reduction's relative
+  error is its longest addition chain times U32 (``step_chain``, ``freeu_chain``: the chains of the kernels' documented reduction orders), not its
+  length.  One term is measured, not derived: ``TOL_NOISE``, the error the device's ``logf`` / ``sincospif`` leave on a generated normal.
+
+Every function of the C ABI is in exactly one of ``REF`` (audited) and ``NOT_AUDITED`` (outside the audit, with the reason).  A buffer whose extent
+depends on the contents of another one (the coefficient row by the step counter, the token table by the ids) is listed in ``DEPENDENT``.
+
 Two kinds of error term.  ``det``: worst-case terms (accumulation, the erf approximation, norm statistics), added as they are.  ``sig``: the
 documented fp16 roundings of intermediates (q, P, the normalised rows, the attention context).  Each is an independent rounding bounded by
 +-U16 |t|, so a sum of many of them through a linear stage adds in quadrature: ``sig = sqrt(Sum (U16 t_j w_j)^2)``, a standard deviation
@@ -39,7 +46,7 @@ from typing import Callable, Dict, Optional
 
 import torch
 
-F16, F32, I32 = torch.float16, torch.float32, torch.int32
+F16, F32, I32, I64 = torch.float16, torch.float32, torch.int32, torch.int64
 U16, SUB16, U32 = 2.0 ** -11, 2.0 ** -25, 2.0 ** -24
 STORE16_REL, STORE16_ABS = 2.0 ** -10, 2.0 ** -24
 STORE32_REL = 2.0 ** -23
@@ -864,6 +871,428 @@ def ref_posterior(a, v):
     return {"out": expect(out.reshape(1, -1), term.reshape(1, -1), F32)}
 
 
+# ===================================================================================================================== guided / stochastic / PAG steps
+#: measured, not derived: ``tests/test_sampler_gpu.py``'s ``TOL_NOISE`` - the largest |z_kernel - z_fp64| the device's ``logf`` / ``sincospif`` /
+#: ``sqrtf`` leave on a Box-Muller normal (their error is no IEEE quantity), with that file's margin of four
+TOL_NOISE = 4 * 5.477e-7
+
+
+def _f32(x) -> float:
+    """A host scalar as the launcher receives it: rounded to fp32."""
+    return torch.tensor(float(x), dtype=F32).item()
+
+
+def _opt(p, name) -> bool:
+    """An optional pointer (absent from the shorter argument lists of the same family counts as NULL)."""
+    return bool(getattr(p, name, 0) or 0)
+
+
+def step_reads(p):
+    """(eps_image is read, eps_perturbed is read): the launcher's own substitutions - equal scales cancel the eps_image terms, a zero g_pag the
+    perturbed term; the pointer is then not dereferenced."""
+    return (_opt(p, "eps_image") and _f32(p.g_image) != _f32(p.g_text)), (_opt(p, "eps_perturbed") and _f32(getattr(p, "g_pag", 0.0)) != 0.0)
+
+
+def layout_step(p):
+    n = p.batch * p.channels * p.hw
+    three, pag = step_reads(p)
+    L = {"eps_uncond": Buf(F32, 1, n, 0), "eps_cond": Buf(F32, 1, n, 0), "latents": Buf(F32, 1, n, 0, "inout"), "x0_prev": Buf(F32, 1, n, 0, "inout"),
+         "coef": None, "state": Buf(I32, 1, 2, 2)}
+    if three:
+        L["eps_image"] = Buf(F32, 1, n, 0)
+    if pag:
+        L["eps_perturbed"] = Buf(F32, 1, n, 0)
+    if _opt(p, "rng"):
+        L["rng"] = Buf(I32, 1, 4, 4)
+    if _opt(p, "mask"):
+        L.update(mask=Buf(F32, p.batch, p.hw, p.hw), known=Buf(F32, 1, n, 0), noise=Buf(F32, 1, n, 0))
+    return L
+
+
+def step_chain(chw: int) -> int:
+    """Longest fp32 addition chain of the per-sample reductions of ``cfg_dpm_step_guided_kernel`` over ``chw`` elements: one workgroup of
+    min(1024, nv rounded up to whole waves) threads (nv = chw / 4 float4s), each adding its 4 x trips elements in order, a 6-level shuffle tree inside
+    the wave, then the wave slots in wave order.  A sum of same-sign terms is within ``chain x U32`` of exact, relative."""
+    nv = max(chw // 4, 1)
+    threads = 1024 if nv >= 1024 else (nv + 63) // 64 * 64
+    return 4 * ((nv + threads - 1) // threads) + 6 + threads // 64
+
+
+def ref_step(p, v):
+    """pv_cfg_dpm_step_guided / _stochastic / _pag from the header, per sample b over chw = channels * hw elements, row {ca, cb, cx, c0, c1, q0, q1, cn}:
+        e = eu + g_text (ec - eu)   |   eu + g_image (em - eu) + g_text (ec - em)          (+ g_pag (ec - ep))
+        f = rescale std_b(ec) / std_b(e) + 1 - rescale  (rescale > 0 and std_b(e) > 0, else 1);  e = f e
+        x0 = ca x + cb e;  x' = cx x + c0 x0 + c1 x0_prev (+ cn z);  with a mask  latents = m x' + (1 - m) (q0 known + q1 noise)
+    z: ``oracle.philox`` from the rng words and the step index, both read from the device buffers.
+
+    Bounds.  Every fp32 operation rounds within U32 of its own result (a fused multiply-add only removes roundings): in e each difference, its product
+    with the scale and the running sum; in x0 = ca x + cb e the two products (U32 of their magnitudes M(x0) together) and the sum (at most M(x0) again);
+    in x' three products (U32 M(x') together) and two sums: 3 U32 M(x'); the noise adds a product and a sum.
+    The factor f (the rescale term; L = ``step_chain(chw)`` accounts for the two reductions over chw elements): with s = sqrt(sum of squared deviations),
+        E(s) = (L / 2 + 2) U32 s            the sum's chain (relative L U32 on the sum, half on its root), the squares and the root
+             + KAPPA eps                    the deviations' own roundings eps = max(err(e)) + U32 max|d|: independent over the elements, so
+                                            2 sum d_i eps_i is a random sum of deviation 2 eps s - on s itself eps, taken KAPPA times
+             + chw delta^2 / (2 s)          the mean's error delta = L U32 mean|v| + max err(v) + U32 |mean|: first order it cancels (sum d_i = 0)
+        err(f) = rescale (E(s_c) / s_e + s_c E(s_e) / s_e^2) + 4 U32 (rescale s_c / s_e + |1 - rescale|)
+    and err(f e) = |f| err(e) + |e| err(f) + U32 |f e|.  A sample with s_e = 0 in fp64 has f = 1 and err(f) = 0: that is the header's contract
+    when the fp32 sums are exact too (an all-zero sample; a constant sample of dyadic values, as the catalogue's).  A constant sample whose fp32
+    mean rounds has an undetermined f in the kernel - 0 / 0 of rounding residue - and no finite bound; the term chw delta^2 / (2 s) says so as s -> 0.
+    The noise term: |cn| TOL_NOISE - a MEASURED number (the device's logf / sincospif are not IEEE operations), tests/test_sampler_gpu.py's."""
+    B, chw = p.batch, p.channels * p.hw
+    c = v["coef"].reshape(-1).double().cpu().tolist()
+    ca, cb, cx, c0, c1, q0, q1, cn = c[:8]
+    gt, gi, gp, rs = _f32(p.g_text), _f32(p.g_image), _f32(getattr(p, "g_pag", 0.0)), _f32(p.rescale)
+    three, pag = step_reads(p)
+    u, cc, x, xp = (f64(v[k]).reshape(B, chw) for k in ("eps_uncond", "eps_cond", "latents", "x0_prev"))
+    # err(e): every operation's rounding is within U32 of ITS result - the difference, its product with the scale (twice the product's magnitude covers
+    # both), the running sum
+    if three:
+        m_ = f64(v["eps_image"]).reshape(B, chw)
+        part = u + gi * (m_ - u)
+        e = part + gt * (cc - m_)
+        ee = U32 * (2 * (gi * (m_ - u)).abs() + part.abs() + 2 * (gt * (cc - m_)).abs() + e.abs())
+    else:
+        e = u + gt * (cc - u)
+        ee = U32 * (2 * (gt * (cc - u)).abs() + e.abs())
+    if pag:
+        pp = f64(v["eps_perturbed"]).reshape(B, chw)
+        e = e + gp * (cc - pp)
+        ee = ee + U32 * (2 * (gp * (cc - pp)).abs() + e.abs())
+    if rs > 0:
+        L = step_chain(chw)
+
+        def root(t, err):
+            mean = t.mean(1, keepdim=True)
+            d = t - mean
+            s = d.pow(2).sum(1, keepdim=True).sqrt()
+            eps = err.amax(1, keepdim=True) + U32 * d.abs().amax(1, keepdim=True)
+            delta = L * U32 * t.abs().mean(1, keepdim=True) + err.amax(1, keepdim=True) + U32 * mean.abs()
+            return s, (L / 2 + 2) * U32 * s + KAPPA * eps + chw * delta ** 2 / (2 * s.clamp_min(1e-300))
+        sc, Ec = root(cc, torch.zeros_like(cc))
+        se, Ee = root(e, ee)
+        live = se > 0
+        sden = torch.where(live, se, torch.ones_like(se))
+        f = torch.where(live, rs * sc / sden + (1 - rs), torch.ones_like(se))
+        ef = torch.where(live, rs * (Ec / sden + sc * Ee / sden ** 2) + 4 * U32 * (rs * sc / sden + abs(1 - rs)), torch.zeros_like(se))
+        ee = f.abs() * ee + e.abs() * ef + U32 * (f * e).abs()
+        e = f * e
+    x0 = ca * x + cb * e
+    mx0 = abs(ca) * x.abs() + abs(cb) * e.abs()
+    ex0 = abs(cb) * ee + 2 * U32 * mx0
+    xn = cx * x + c0 * x0 + c1 * xp
+    mx = abs(cx) * x.abs() + abs(c0) * (mx0 + ex0) + abs(c1) * xp.abs()
+    exn = abs(c0) * ex0 + 3 * U32 * mx
+    if "rng" in v:
+        from .philox import noise_from_words
+        z = noise_from_words(v["rng"].reshape(-1).cpu().tolist(), B, chw, step_index(v["state"])).to(x.device)
+        xn = xn + cn * z
+        exn = exn + abs(cn) * TOL_NOISE + 2 * U32 * (mx + abs(cn) * z.abs())
+    if "mask" in v:
+        m = f64(v["mask"]).reshape(B, 1, p.hw).expand(B, p.channels, p.hw).reshape(B, chw)
+        kn, nz = f64(v["known"]).reshape(B, chw), f64(v["noise"]).reshape(B, chw)
+        k = q0 * kn + q1 * nz
+        mk = abs(q0) * kn.abs() + abs(q1) * nz.abs()
+        mag = m.abs() * (xn.abs() + exn) + (1 - m).abs() * mk
+        xn, exn = m * xn + (1 - m) * k, m.abs() * exn + 2 * U32 * (1 - m).abs() * mk + 3 * U32 * mag
+    return {"latents": expect(xn.reshape(1, -1), exn.reshape(1, -1), F32), "x0_prev": expect(x0.reshape(1, -1), ex0.reshape(1, -1), F32)}
+
+
+def layout_fusion_draw(p):
+    L = {"rng": Buf(I32, 1, 4, 4, "inout"), "out": Buf(F32, p.n_layers, 2, 2, "out")}
+    if _opt(p, "state"):
+        L["state"] = Buf(I32, 1, 2, 2)
+    if _opt(p, "forced"):
+        L["forced"] = Buf(F32, 1, p.n_layers, p.n_layers)
+    return L
+
+
+def ref_fusion_draw(p, v):
+    """out[layer] = (w_text, w_ip): u < rule1 -> (scale, 0); u > rule2 -> (0, scale); else (1, 1), u = ``oracle.philox.fusion_uniform`` of the rng
+    words (forced[layer] >= 0 replaces it); with only_last_step and a state the rule holds at state[0] == state[1] - 1 alone.  rng[2] advances by one.
+    Every value is exact: u has 24 bits, the comparisons are fp32 ones, the outputs are the fp32 scale, 0 or 1."""
+    from .philox import fusion_uniform
+    n = p.n_layers
+    words = v["rng"].reshape(-1).cpu().tolist()
+    u = torch.from_numpy(fusion_uniform(words, n))
+    if "forced" in v:
+        fo = f64(v["forced"]).reshape(-1).cpu()
+        u = torch.where(fo >= 0, fo, u)
+    on = True
+    if p.only_last_step and "state" in v:
+        s = v["state"].reshape(-1).cpu().tolist()
+        on = s[0] == s[1] - 1
+    sc, r1, r2 = _f32(p.scale), _f32(p.rule1), _f32(p.rule2)
+    out = torch.ones(n, 2, dtype=torch.float64)
+    if on:
+        out[u < r1] = torch.tensor([sc, 0.0], dtype=torch.float64)
+        out[(u >= r1) & (u > r2)] = torch.tensor([0.0, sc], dtype=torch.float64)
+    dev = v["out"].device
+    nxt = list(words)
+    nxt[2] = ((int(words[2]) & 0xFFFFFFFF) + 1) & 0xFFFFFFFF
+    nxt[2] -= (1 << 32) if nxt[2] >= (1 << 31) else 0
+    return {"out": Expect(out.to(dev), torch.zeros(n, 2, dtype=torch.float64, device=dev), 0.0, None),
+            "rng": Expect(torch.tensor([nxt], dtype=torch.float64, device=dev), torch.zeros(1, 4, dtype=torch.float64, device=dev), 0.0, None)}
+
+
+# ===================================================================================================================== FreeU, resize, pointwise fp32
+def layout_freeu(p):
+    rows = p.batch * p.h * p.w
+    L = {}
+    if _opt(p, "x"):
+        L.update(x=Buf(F16, rows, p.cx, p.ldx), x_out=Buf(F16, rows, p.cx, p.ldxo, "out"))
+    if _opt(p, "skip"):
+        L.update(skip=Buf(F16, rows, p.cs, p.lds), skip_out=Buf(F16, rows, p.cs, p.ldso, "out"))
+    return L
+
+
+def freeu_chain(hw: int) -> int:
+    """Longest fp32 chain of one of pv_freeu_rows' seven plane sums: 16 pixel lanes of ceil(hw / 16) terms each, then the lanes in order."""
+    return (hw + 15) // 16 + 16
+
+
+def ref_freeu(p, v):
+    """Backbone: x_out = fp16(float(x) * b) in the first cx / 2 columns (one fp32 product), the other columns bit for bit.  Skip: per (image, channel)
+    plane the frequencies (u, v) in {0, -1}^2 times s, in the header's closed form  p + (s - 1) / (h w) Sum_{u,v} Re(X[u,v] e^{+2 pi i (u y/h + v x/w)}).
+    Bound of the skip, with L = ``freeu_chain(hw)`` and S = Sum|p| over the plane: each of the seven sums is an fp32 chain of L terms p x (a cosine /
+    sine: sincospif's 2 ulps, the angle sum's two products and sum 4 more), so within (L + 6) U32 S; it is scaled once (1), multiplied with such a cosine /
+    sine again (6 + 1) and added (1): (L + 15) U32 S per term, seven terms, times |s - 1| / (h w); then one fp32 add before the fp16 store."""
+    res = {}
+    B, h, w = p.batch, p.h, p.w
+    if "x" in v:
+        x = f64(v["x"])
+        half = p.cx // 2
+        b = _f32(p.b)
+        ref = x.clone()
+        ref[:, :half] *= b
+        det = torch.zeros_like(ref)
+        det[:, :half] = U32 * ref[:, :half].abs()
+        res["x_out"] = expect(ref, det, F16)
+        res["x_out (upper half)"] = Expect(x[:, half:], torch.zeros_like(x[:, half:]), 0.0, None, derive=lambda got, half=half: got["x_out"][:, half:])
+    if "skip" in v:
+        sk = f64(v["skip"])
+        s = _f32(p.s)
+        pl = sk.reshape(B, h, w, p.cs)
+        yy = (torch.arange(h, dtype=torch.float64, device=sk.device) / h).view(1, h, 1, 1)
+        xx = (torch.arange(w, dtype=torch.float64, device=sk.device) / w).view(1, 1, w, 1)
+        upd = torch.zeros_like(pl)
+        for fu in (0, -1):
+            for fv in (0, -1):
+                ph = 2 * math.pi * (fu * yy + fv * xx)
+                Xr = (pl * torch.cos(ph)).sum((1, 2), keepdim=True)          # X = Sum p e^{-i ph}
+                Xi = -(pl * torch.sin(ph)).sum((1, 2), keepdim=True)
+                upd = upd + Xr * torch.cos(ph) - Xi * torch.sin(ph)          # Re(X e^{+i ph})
+        k = (s - 1.0) / (h * w)
+        ref = pl + k * upd
+        sabs = pl.abs().sum((1, 2), keepdim=True)
+        det = abs(k) * 7 * (freeu_chain(h * w) + 15) * U32 * sabs + U32 * ref.abs()
+        res["skip_out"] = expect(ref.reshape(-1, p.cs), det.expand_as(ref).reshape(-1, p.cs), F16)
+    return res
+
+
+def bilinear_taps(n_in: int, n_out: int, device):
+    """One axis of F.interpolate(mode="bilinear", align_corners=False): src = max((dst + 0.5) in / out - 0.5, 0) as the exact ratio
+    ((2 dst + 1) in - out) / (2 out), i0 = floor(src), i1 = min(i0 + 1, in - 1), weight = src - i0."""
+    dst = torch.arange(n_out, dtype=torch.float64, device=device)
+    src = (((2 * dst + 1) * n_in - n_out) / (2 * n_out)).clamp_min(0)
+    i0 = src.floor().long().clamp_max(n_in - 1)
+    return i0, (i0 + 1).clamp_max(n_in - 1), src - i0
+
+
+def layout_resize(p):
+    planes = p.batch * p.channels
+    L = {"x": Buf(F32, 1, planes * p.h * p.w, 0), "out": Buf(F32, 1, planes * p.oh * p.ow, 0, "out")}
+    if _opt(p, "ca"):
+        L["ca"] = Buf(F32, 1, p.batch, p.batch)
+    if _opt(p, "y"):
+        L.update(y=Buf(F32, 1, planes * p.oh * p.ow, 0), cb=Buf(F32, 1, p.batch, p.batch))
+    return L
+
+
+def ref_resize(p, v):
+    """out[b][c] = ca[b] bilinear(x[b][c]: h x w -> oh x ow) (+ cb[b] y[b][c]); a weight of exactly 0 returns the tap itself (no 0 x b product).
+    Bound: a mix (1 - t) a + t b rounds the weight, 1 - t, two products and a sum - 5 U32 of its magnitudes; two levels of it; then the product with ca
+    and the product and sum with cb y: 3 U32 of theirs."""
+    B, C_ = p.batch, p.channels
+    x = f64(v["x"]).reshape(B, C_, p.h, p.w)
+    y0, y1, wy = bilinear_taps(p.h, p.oh, x.device)
+    x0, x1, wx = bilinear_taps(p.w, p.ow, x.device)
+    wy = wy.view(p.oh, 1)
+
+    def mix(a, b, t):
+        return torch.where(t == 0, a, (1 - t) * a + t * b)
+    top, bot = mix(x[:, :, y0][..., x0], x[:, :, y0][..., x1], wx), mix(x[:, :, y1][..., x0], x[:, :, y1][..., x1], wx)
+    r = mix(top, bot, wy)
+    xa = x.abs()
+    mag = mix(mix(xa[:, :, y0][..., x0], xa[:, :, y0][..., x1], wx), mix(xa[:, :, y1][..., x0], xa[:, :, y1][..., x1], wx), wy)
+    det = 10 * U32 * mag
+    if "ca" in v:
+        ca = f64(v["ca"]).reshape(B, 1, 1, 1)
+        r, mag, det = ca * r, ca.abs() * mag, ca.abs() * det
+    if "y" in v:
+        t = f64(v["cb"]).reshape(B, 1, 1, 1) * f64(v["y"]).reshape(B, C_, p.oh, p.ow)
+        r, mag = r + t, mag + t.abs()
+    if "ca" in v or "y" in v:
+        det = det + 3 * U32 * mag
+    return {"out": expect(r.reshape(1, -1), det.reshape(1, -1), F32)}
+
+
+def layout_affine_rows(p):
+    n = p.per_sample * p.batch
+    L = {"x": Buf(F32, 1, n, 0), "ca": Buf(F32, 1, p.batch, p.batch), "out": Buf(F32, 1, n, 0, "out")}
+    if _opt(p, "y"):
+        L.update(y=Buf(F32, 1, n, 0), cb=Buf(F32, 1, p.batch, p.batch))
+    return L
+
+
+def ref_affine_rows(p, v):
+    """out[b][i] = ca[b] x[b][i] (+ cb[b] y[b][i]): one product (the store's rounding), or two products and a sum: 2 U32 of the magnitudes."""
+    B = p.batch
+    r = f64(v["ca"]).reshape(B, 1) * f64(v["x"]).reshape(B, p.per_sample)
+    det = torch.zeros_like(r)
+    if "y" in v:
+        t = f64(v["cb"]).reshape(B, 1) * f64(v["y"]).reshape(B, p.per_sample)
+        det = 2 * U32 * (r.abs() + t.abs())
+        r = r + t
+    return {"out": expect(r.reshape(1, -1), det.reshape(1, -1), F32)}
+
+
+def layout_composite(p):
+    n = p.batch * p.channels * p.hw
+    return {"gen": Buf(F32, 1, n, 0), "orig": Buf(F32, 1, n, 0), "mask": Buf(F32, p.batch, p.hw, p.hw), "out": Buf(F32, 1, n, 0, "out")}
+
+
+def ref_composite(p, v):
+    """out = clamp(m gen + (1 - m) orig, lo, hi), m [B][1][hw] over the channels; out may be gen.  1 - m, two products, a sum: 4 U32 of the magnitudes
+    (the clamp only moves a value towards the reference's)."""
+    B, hw = p.batch, p.hw
+    m = f64(v["mask"]).reshape(B, 1, hw).expand(B, p.channels, hw).reshape(1, -1)
+    g, o = f64(v["gen"]), f64(v["orig"])
+    r = (m * g + (1 - m) * o).clamp(_f32(p.lo), _f32(p.hi))
+    return {"out": expect(r, 4 * U32 * ((m * g).abs() + ((1 - m) * o).abs()), F32)}
+
+
+def layout_clamp(p):
+    return {"x": Buf(F32, 1, p.n, 0, "inout")}
+
+
+def ref_clamp(p, v):
+    """In place, exact."""
+    r = f64(v["x"]).clamp(_f32(p.lo), _f32(p.hi))
+    return {"x": Expect(r, torch.zeros_like(r), 0.0, None)}
+
+
+# ===================================================================================================================== conditioning front ends
+def layout_rows_mean(p):
+    return {"x": Buf(F16, (p.groups - 1) * p.group_rows + p.count, p.cols, p.ldx), "y": Buf(F16, p.groups, p.cols, p.ldy, "inout" if p.accumulate else "out")}
+
+
+def ref_rows_mean(p, v):
+    """y[g] (+)= mean of the ``count`` rows from g * group_rows on.  fp32: eight row lanes of ceil(count / 8) terms each, then the lanes in order - a chain
+    of ceil(count / 8) + 8 on Sum|x| -, the division and the sum with the previous y: 2 U32 of their magnitudes."""
+    x = f64(v["x"])
+    idx = (torch.arange(p.groups, device=x.device) * p.group_rows)[:, None] + torch.arange(p.count, device=x.device)[None, :]
+    blk = x[idx]                                                     # [groups, count, cols]
+    mean, mabs = blk.mean(1), blk.abs().mean(1)
+    prev = f64(v["y"]) if p.accumulate else torch.zeros_like(mean)
+    det = ((p.count + 7) // 8 + 8) * U32 * mabs + 2 * U32 * (mean.abs() + prev.abs())
+    return {"y": expect(mean + prev, det, F16)}
+
+
+def round_f16(x: torch.Tensor) -> torch.Tensor:
+    """fp64 values rounded to the fp16 grid, to nearest, ties to even, overflow (>= 65520) to infinity - in integer steps of the value's quantum
+    2^(max(e, -14) - 10), written out here and not through a library cast."""
+    ax = x.abs()
+    _, ex = torch.frexp(ax.clamp_min(2.0 ** -30))                    # ax = m 2^ex, m in [0.5, 1): e = ex - 1
+    k = (ex - 1).clamp(-14, 16).long() - 10                          # a table of exact powers of two (a device's pow() need not be exact)
+    q = torch.tensor([2.0 ** i for i in range(-24, 7)], dtype=torch.float64, device=x.device)[k + 24]
+    r = torch.round(ax / q) * q                                      # torch.round: half to even; the division by a power of two is exact
+    r = torch.where(r >= 65520.0, torch.full_like(r, float("inf")), r)
+    r = torch.where(torch.isinf(ax), ax, r)
+    return torch.copysign(r, x)
+
+
+def _bits16(t):
+    return t.contiguous().view(torch.int16)
+
+
+def layout_cast_to_f16(p):
+    return {"x": Buf(F32, 1, p.n, 0), "y": Buf(F16, 1, p.n, 0, "out")}
+
+
+def ref_cast_to_f16(p, v):
+    """Round to nearest even, overflow to infinity, signed zeros kept: exact (value and sign bit)."""
+    r = round_f16(f64(v["x"]))
+    z = torch.zeros_like(r)
+    return {"y": Expect(r, z, 0.0, None), "y (sign)": Expect(torch.signbit(r).double(), z, 0.0, None, derive=lambda got: torch.signbit(got["y"]))}
+
+
+def layout_cast_to_f32(p):
+    return {"x": Buf(F16, 1, p.n, 0), "y": Buf(F32, 1, p.n, 0, "out")}
+
+
+def ref_cast_to_f32(p, v):
+    """Exact: every fp16 value (subnormals, infinities, signed zeros) is an fp32 value."""
+    r = f64(v["x"])
+    z = torch.zeros_like(r)
+    return {"y": Expect(r, z, 0.0, None), "y (sign)": Expect(torch.signbit(r).double(), z, 0.0, None, derive=lambda got: torch.signbit(got["y"]))}
+
+
+def layout_patchify(p):
+    g = p.img // p.patch
+    return {"x": Buf(F32, 1, p.batch * p.ch * p.img * p.img, 0), "out": Buf(F16, p.batch * g * g, p.kpad, p.kpad, "out")}
+
+
+def ref_patchify(p, v):
+    """Row = one patch in (channel, py, px) order, rounded to fp16, zero padded to kpad (the padding is output): exact."""
+    g, P = p.img // p.patch, p.patch
+    x = f64(v["x"]).reshape(p.batch, p.ch, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(p.batch * g * g, p.ch * P * P)
+    out = torch.zeros(p.batch * g * g, p.kpad, dtype=torch.float64, device=x.device)
+    out[:, :p.ch * P * P] = round_f16(x)
+    return {"out": Expect(out, torch.zeros_like(out), 0.0, None)}
+
+
+def layout_vision_embed(p):
+    return {"patches": Buf(F16, p.batch * (p.ntok - 1), p.dim, p.dim), "cls": Buf(F32, 1, p.dim, p.dim), "pos": Buf(F32, p.ntok, p.dim, p.dim),
+            "out": Buf(F16, p.batch * p.ntok, p.dim, p.dim, "out")}
+
+
+def ref_vision_embed(p, v):
+    """out[b][0] = cls + pos[0]; out[b][1 + i] = patches[b][i] + pos[1 + i]: one fp32 sum, then the fp16 store."""
+    B, T, dim = p.batch, p.ntok, p.dim
+    tokv = torch.cat([f64(v["cls"]).reshape(1, 1, dim).expand(B, 1, dim), f64(v["patches"]).reshape(B, T - 1, dim)], 1)
+    pos = f64(v["pos"]).reshape(1, T, dim)
+    return {"out": expect((tokv + pos).reshape(B * T, dim), (U32 * (tokv.abs() + pos.abs())).reshape(B * T, dim), F16)}
+
+
+def layout_text_embed(p):
+    L = {"ids": Buf(I64, p.batch, p.seq, p.seq), "tok": None, "pos": Buf(F32, p.seq, p.dim, p.dim), "out": Buf(F16, p.batch * p.seq, p.dim, p.dim, "out")}
+    if p.n_concept > 0:
+        L.update(concept=Buf(F16, p.batch * p.n_concept, p.dim, p.dim), placeholder_idx=Buf(I64, 1, p.batch, p.batch))
+    return L
+
+
+def ref_text_embed(p, v):
+    """Row j of sample b: tok[ids[b][j]] before the placeholder position i = placeholder_idx[b], concept[b][j - i] on the n_concept positions from it,
+    tok[ids[b][j - n_concept + 1]] behind (the tail shifted right by n_concept - 1, truncated); + pos[j]: one fp32 sum, then the fp16 store.
+    n_concept == 0: the stock embedding (placeholder_idx and concept are not read)."""
+    B, S, dim, E = p.batch, p.seq, p.dim, p.n_concept
+    ids = v["ids"].reshape(B, S).long()
+    tok = f64(v["tok"])
+    j = torch.arange(S, device=ids.device)[None, :].expand(B, S)
+    if E > 0:
+        i = v["placeholder_idx"].reshape(B, 1).long()
+        src = torch.where(j < i, j, (j - E + 1).clamp(0, S - 1))
+        val = tok[torch.gather(ids, 1, src)]
+        inside = (j >= i) & (j < i + E)
+        con = f64(v["concept"]).reshape(B, E, dim)
+        cj = (j - i).clamp(0, E - 1)
+        val = torch.where(inside[..., None], torch.gather(con, 1, cj[..., None].expand(B, S, dim)), val)
+    else:
+        val = tok[ids]
+    pos = f64(v["pos"]).reshape(1, S, dim)
+    return {"out": expect((val + pos).reshape(B * S, dim), (U32 * (val.abs() + pos.abs())).reshape(B * S, dim), F16)}
+
+
 # ===================================================================================================================== tables
 #: positional argument names of the launchers that take no parameter struct (``_lib.SIGNATURES`` order, stream excluded)
 ARGS = {
@@ -878,6 +1307,24 @@ ARGS = {
     "pv_softmax_rows": ("x", "ld", "rows", "cols", "scale"),
     "pv_posterior_sample": ("moments", "eps", "out", "batch", "chw"),
     "pv_groupnorm_scale_shift": ("table",),       # after the struct
+    "pv_cfg_dpm_step_guided": ("eps_uncond", "eps_image", "eps_cond", "latents", "x0_prev", "coef", "state", "g_text", "g_image", "rescale", "mask", "known",
+                               "noise", "batch", "channels", "hw"),
+    "pv_cfg_dpm_step_stochastic": ("eps_uncond", "eps_image", "eps_cond", "latents", "x0_prev", "coef", "state", "rng", "g_text", "g_image", "rescale", "mask",
+                                   "known", "noise", "batch", "channels", "hw"),
+    "pv_cfg_dpm_step_pag": ("eps_uncond", "eps_image", "eps_cond", "eps_perturbed", "latents", "x0_prev", "coef", "state", "rng", "g_text", "g_image", "g_pag",
+                            "rescale", "mask", "known", "noise", "batch", "channels", "hw"),
+    "pv_fusion_draw": ("state", "rng", "forced", "out", "n_layers", "rule1", "rule2", "scale", "only_last_step"),
+    "pv_freeu_rows": ("x", "ldx", "cx", "x_out", "ldxo", "b", "skip", "lds", "cs", "skip_out", "ldso", "s", "batch", "h", "w"),
+    "pv_resize_bilinear_affine_f32": ("x", "y", "ca", "cb", "out", "batch", "channels", "h", "w", "oh", "ow"),
+    "pv_affine_rows_f32": ("x", "y", "ca", "cb", "out", "per_sample", "batch"),
+    "pv_composite_clamp_f32": ("gen", "orig", "mask", "out", "lo", "hi", "batch", "channels", "hw"),
+    "pv_clamp_f32": ("x", "lo", "hi", "n"),
+    "pv_rows_mean": ("x", "ldx", "y", "ldy", "groups", "count", "group_rows", "cols", "accumulate"),
+    "pv_cast_f32_to_f16": ("x", "y", "n"),
+    "pv_cast_f16_to_f32": ("x", "y", "n"),
+    "pv_patchify": ("x", "out", "batch", "ch", "img", "patch", "kpad"),
+    "pv_clip_vision_embed": ("patches", "cls", "pos", "out", "batch", "ntok", "dim"),
+    "pv_clip_text_embed": ("ids", "tok", "pos", "concept", "placeholder_idx", "n_concept", "out", "batch", "seq", "dim"),
 }
 
 LAYOUT = {
@@ -888,6 +1335,11 @@ LAYOUT = {
     "pv_im2col3x3": layout_im2col, "pv_conv_out": layout_conv_out, "pv_timestep_embedding": layout_timestep, "pv_cfg_dpm_step": layout_cfg,
     "pv_step_advance": layout_step_advance, "pv_pointwise_nchw": layout_pointwise, "pv_softmax_rows": layout_softmax_rows,
     "pv_posterior_sample": layout_posterior, "pv_cfg_dpm_step_masked": layout_cfg_masked,
+    "pv_cfg_dpm_step_guided": layout_step, "pv_cfg_dpm_step_stochastic": layout_step, "pv_cfg_dpm_step_pag": layout_step, "pv_fusion_draw": layout_fusion_draw,
+    "pv_freeu_rows": layout_freeu, "pv_resize_bilinear_affine_f32": layout_resize, "pv_affine_rows_f32": layout_affine_rows,
+    "pv_composite_clamp_f32": layout_composite, "pv_clamp_f32": layout_clamp, "pv_rows_mean": layout_rows_mean, "pv_cast_f32_to_f16": layout_cast_to_f16,
+    "pv_cast_f16_to_f32": layout_cast_to_f32, "pv_patchify": layout_patchify, "pv_clip_vision_embed": layout_vision_embed,
+    "pv_clip_text_embed": layout_text_embed,
 }
 
 REF = {
@@ -897,6 +1349,42 @@ REF = {
     "pv_groupnorm_apply": ref_gn_apply, "pv_im2col3x3": ref_im2col, "pv_conv_out": ref_conv_out, "pv_timestep_embedding": ref_timestep,
     "pv_cfg_dpm_step": ref_cfg, "pv_step_advance": ref_step_advance, "pv_pointwise_nchw": ref_pointwise, "pv_softmax_rows": ref_softmax_rows,
     "pv_posterior_sample": ref_posterior, "pv_cfg_dpm_step_masked": ref_cfg_masked,
+    "pv_cfg_dpm_step_guided": ref_step, "pv_cfg_dpm_step_stochastic": ref_step, "pv_cfg_dpm_step_pag": ref_step, "pv_fusion_draw": ref_fusion_draw,
+    "pv_freeu_rows": ref_freeu, "pv_resize_bilinear_affine_f32": ref_resize, "pv_affine_rows_f32": ref_affine_rows, "pv_composite_clamp_f32": ref_composite,
+    "pv_clamp_f32": ref_clamp, "pv_rows_mean": ref_rows_mean, "pv_cast_f32_to_f16": ref_cast_to_f16, "pv_cast_f16_to_f32": ref_cast_to_f32,
+    "pv_patchify": ref_patchify, "pv_clip_vision_embed": ref_vision_embed, "pv_clip_text_embed": ref_text_embed,
+}
+
+
+def _coef_rows(p, state):
+    return Buf(F32, 1, (step_index(state) + 1) * 8, 0)
+
+
+#: launchers with a buffer whose extent depends on the CONTENTS of another (device-resident) buffer: launcher -> (the buffer read first, the dependent
+#: buffer, extent(p, first view) -> Buf, the width of the row the reference is handed - 0: the whole buffer).  The step launchers index the coefficient
+#: table with the clamped step index of ``state``; the text embedding gathers rows of ``tok`` by ``ids`` (the vocabulary size is no argument).
+DEPENDENT = {
+    "pv_timestep_embedding": ("state", "timesteps", lambda p, s: Buf(F32, 1, step_index(s) + 1, 0), 0),
+    **{n: ("state", "coef", _coef_rows, 8) for n in ("pv_cfg_dpm_step", "pv_cfg_dpm_step_masked", "pv_cfg_dpm_step_guided", "pv_cfg_dpm_step_stochastic",
+                                                     "pv_cfg_dpm_step_pag")},
+    "pv_clip_text_embed": ("ids", "tok", lambda p, ids: Buf(F32, int(ids.max().item()) + 1, p.dim, p.dim), 0),
+}
+
+_BWD = "backward / training launcher: the training tape's audit is a separate piece of work"
+_OPT = "optimizer launcher: outside the inference audit"
+_QUERY = "a host-side query: launches nothing"
+#: every other symbol of ``photoverse_amd._lib.SIGNATURES``: deliberately outside the launch audit, and why.  A launcher is in exactly one of REF and
+#: this table (tests/test_abi_ref_cpu.py); nothing a plan of ``run_inference`` / ``generate.py`` can record may be listed here.
+NOT_AUDITED = {
+    "pv_abi_version": _QUERY, "pv_device_count": _QUERY, "pv_xattn_fused_wo_slot": _QUERY,
+    "pv_gemm_conv_kernel_info": _QUERY + " (the dispatch rule the edge catalogue asks)", "pv_attention_kernel_info": _QUERY + " (the dispatch rule the edge catalogue asks)",
+    **{n: _BWD for n in ("pv_cross_attention_backward", "pv_transpose_f16", "pv_layernorm_backward", "pv_reduce_blocks", "pv_colsum_f16", "pv_attention_backward",
+                         "pv_groupnorm_backward", "pv_geglu_backward", "pv_act_backward", "pv_add_rows_f16", "pv_dilate2x", "pv_pool2x_sum", "pv_dropout_f16",
+                         "pv_gray_resize_backward", "pv_wgrad_tn", "pv_softmax_rows_backward", "pv_clamp_mask_f32", "pv_sign_f32", "pv_gather_rows_f32",
+                         "pv_pack_weights")},
+    **{n: "forward launcher of the training tape / the face-identity loss only (no inference plan records it): " + _BWD
+       for n in ("pv_geglu", "pv_act_forward", "pv_col_affine_f16", "pv_prelu_f16", "pv_maxpool2x2", "pv_gray_resize", "pv_cosine_embedding_loss", "pv_reduce_mean")},
+    **{n: _OPT for n in ("pv_reduce_sumsq", "pv_sumsq_multi", "pv_clip_coef_groups", "pv_adamw_multi")},
 }
 
 #: struct fields no layout / reference reads, and why.  Every other field of an audited struct is read by its layout or its reference
@@ -919,6 +1407,38 @@ STRUCT_FUNCS = {
     "GroupNormParams": (layout_groupnorm, layout_gn_stats, layout_gn_scale_shift, layout_gn_apply, group_stats, ref_gn_stats, ref_gn_scale_shift,
                         ref_gn_apply),
 }
+
+
+#: per argument-list launcher (``ARGS``) added with the guided / conditioning audit: the functions that read its arguments
+ARG_FUNCS = {
+    **{n: (layout_step, ref_step, step_reads) for n in ("pv_cfg_dpm_step_guided", "pv_cfg_dpm_step_stochastic", "pv_cfg_dpm_step_pag")},
+    "pv_fusion_draw": (layout_fusion_draw, ref_fusion_draw), "pv_freeu_rows": (layout_freeu, ref_freeu),
+    "pv_resize_bilinear_affine_f32": (layout_resize, ref_resize), "pv_affine_rows_f32": (layout_affine_rows, ref_affine_rows),
+    "pv_composite_clamp_f32": (layout_composite, ref_composite), "pv_clamp_f32": (layout_clamp, ref_clamp), "pv_rows_mean": (layout_rows_mean, ref_rows_mean),
+    "pv_cast_f32_to_f16": (layout_cast_to_f16, ref_cast_to_f16), "pv_cast_f16_to_f32": (layout_cast_to_f32, ref_cast_to_f32),
+    "pv_patchify": (layout_patchify, ref_patchify), "pv_clip_vision_embed": (layout_vision_embed, ref_vision_embed),
+    "pv_clip_text_embed": (layout_text_embed, ref_text_embed),
+}
+
+
+def _names_read(fns) -> set:
+    import inspect
+    import re
+    names = set()
+    for fn in fns:
+        for line in inspect.getsource(fn).splitlines():
+            if '"scratch"' in line:
+                continue
+            names |= set(re.findall(r"\bp\.(\w+)", line)) | set(re.findall(r'"(\w+)": (?:Buf\(|None)', line)) | set(re.findall(r'L\["(\w+)"\]', line))
+            names |= set(re.findall(r"(\w+)=Buf\(", line)) | set(re.findall(r'"(\w+)" in v', line)) | set(re.findall(r'v\["(\w+)"\]', line))
+            names |= set(re.findall(r'(?:getattr|_opt|_ptr)\(p, "(\w+)"', line))
+    return names
+
+
+def args_read(launcher: str, funcs=None) -> set:
+    """``fields_read`` for a launcher that takes positional arguments: the names of ``ARGS[launcher]`` its layout / reference functions mention
+    (the same tripwire: an argument added to the ABI and to ``ARGS`` that nobody models is in ``ARGS`` and not here)."""
+    return _names_read(ARG_FUNCS[launcher] if funcs is None else funcs) & set(ARGS[launcher])
 
 
 def fields_read(struct: str) -> set:

@@ -8,10 +8,15 @@ are found by asking ``pv_gemm_conv_kernel_info`` / ``pv_attention_kernel_info`` 
 Every tensor a launch addresses is a guarded view (``guarded_out`` / ``guarded_in``): it sits in the middle of a larger storage with at least
 ``TILE_ROWS`` = 256 rows x ld elements in front and behind (256 rows: the tallest tile of the library, so a whole stray tile stays inside the
 storage the Auditor snapshots), and with a row gap (``ld = cols + 8``) wherever the launcher takes a leading dimension.  Output margins hold the
-byte ``OUT_FILL``; input margins and row gaps hold NaN (0x7fffffff next to integers): an input's described extent is all a launch may depend
+byte ``OUT_FILL``; input margins and row gaps hold NaN (0x7fffffff next to 32-bit integers, -1 next to 64-bit indices): an input's described extent is all a launch may depend
 on, so anything read outside it that reaches a result makes the result non-finite, which the Auditor's finite check reports.  Reads inside an
 arena cannot fault.  ``EdgeRecorder.empty`` guards the buffers the recorder allocates itself (workspaces, statistics, outputs), ``reguard`` the
 inputs it derives at record time (folded weights, row sums).
+
+The launchers of the newer loop features and of the pre-loop conditioning (the guided / stochastic / PAG steps, ``pv_freeu_rows``, the resize, the
+fp32 pointwise ones, ``pv_rows_mean``, the casts, patchify and the two embeds) are not GEMMs: besides their smallest shapes a second group of cases
+(name prefix ``product-``) runs single launches of them at the shapes the product gives them.  A case may promise that two of its launches are the
+same kernel on the same inputs (``rec.same_bits``: pairs of outputs that must agree bit for bit - the launchers' documented substitutions).
 
 With a CPU device the recorder is dry: it builds the same parameter blocks and tags (the ``*_kernel_info`` calls need no GPU) and never runs.
 """
@@ -47,6 +52,10 @@ def _arena(n_front: int, n_body: int, dtype, device, fill, arenas):
         a.view(torch.uint8).fill_(OUT_FILL)
     elif dtype.is_floating_point:
         a = torch.full((total,), float("nan"), dtype=dtype, device=device)
+    elif dtype == torch.int64:
+        # 64-bit integers are row indices (token ids, placeholder positions): -1 lands in the NaN margin in front of the table it indexes, which the
+        # finite check reports; the largest value would send the read far outside every arena
+        a = torch.full((total,), -1, dtype=dtype, device=device)
     else:
         a = torch.full((total,), torch.iinfo(dtype).max, dtype=dtype, device=device)
     if arenas is not None:
@@ -267,6 +276,36 @@ def unguarded(rec) -> List[str]:
             if not _in_arena(rec.arenas, addr, ext, margin):
                 bad.append(f"call {i} ({name}), field {k}")
     return bad
+
+
+def host_views(rec, i: int):
+    """(launcher, params, field -> [rows, cols] view) of call ``i`` of a DRY recorder, resolved through its arenas the way ``plan_audit.Auditor`` resolves a
+    live one through the held storages: what ``abi_ref.REF`` is evaluated on without a GPU."""
+    fn, args = rec.calls[i]
+    name, p, _ = _call_params(fn, args)
+    L = dict(A.LAYOUT[name](p))
+    v = {}
+
+    def resolve(k, buf):
+        addr = getattr(p, k)
+        if not addr:
+            return
+        lo, hi, a = next(e for e in rec.arenas if e[0] <= addr < e[1])
+        assert a.dtype == buf.dtype, (name, k, a.dtype, buf.dtype)
+        ld = buf.ld if buf.ld else buf.cols
+        v[k] = a.as_strided((buf.rows, buf.cols), (ld, 1), (addr - lo) // _isz(buf.dtype))
+
+    dep = A.DEPENDENT.get(name)
+    if dep is not None and L.get(dep[0]) is not None:
+        resolve(dep[0], L[dep[0]])
+        if dep[0] in v:
+            L[dep[1]] = dep[2](p, v[dep[0]])
+    for k, buf in L.items():
+        if k not in v and buf is not None:
+            resolve(k, buf)
+    if dep is not None and dep[3] and dep[1] in v:
+        v[dep[1]] = v[dep[1]][:, A.step_index(v[dep[0]]) * dep[3]:][:, :dep[3]]
+    return name, p, v
 
 
 def reguard(ctx: Ctx):
@@ -711,6 +750,261 @@ def _zero_gemm(c):
 
 add("gemm-cancelling-operands", _cancelling)
 add("gemm-all-zero-input", _zero_gemm)
+
+
+# ============================================================================================================================== guided / stochastic / PAG steps
+STEP_ROWS = 5
+#: (C, h, w) with nv = C h w / 4 float4s per sample: one live lane of the one wave; 36; a second wave with one live lane; 1025 = one thread of the
+#: 1024-thread workgroup takes a second trip of the strided loop.  hw % 4 == 0 is the launchers' rule (the mask is read as float4)
+STEP_SHAPES = {1: (1, 2, 2), 36: (4, 6, 6), 65: (5, 4, 13), 1025: (5, 20, 41)}
+#: rng words with the high bit set in every word; sample offset 0xFFFFFFFE: sample 2 wraps to counter word 0
+STEP_RNG = (0x9E3779B9, 0xDEADBEEF, 0xFFFFFFFE, 0x80000003)
+G_TEXT, G_IMAGE, G_PAG, RESCALE = 7.5, 3.0, 2.0, 0.7
+
+
+def _i32(words):
+    return torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=I32)
+
+
+def _step_coef(c):
+    """5 rows {ca, cb, cx, c0, c1, q0, q1, cn} around a mid-schedule row; the last row is the SDE table's last: cx = 0, c0 = 1, c1 = 0, cn = 0."""
+    tab = torch.tensor([1.0, -0.5, 0.8, 0.6, -0.3, 0.9, 0.4, 0.7]) + 0.1 * c.randn(STEP_ROWS, 8)
+    tab[-1, [2, 3, 4, 7]] = torch.tensor([0.0, 1.0, 0.0, 0.0])
+    return c.put(tab.contiguous())
+
+
+def _step_eps(c, shape, k):
+    """One prediction (B = 3): sample 0 ordinary, sample 1 all zero, sample 2 constant - a dyadic value per prediction, so that every fp32 sum and the
+    mean of the sample are exact and its deviations are exactly 0 beside a mean that is not (std = 0 next to an ordinary sample)."""
+    t = c.randn(*shape)
+    t[1] = 0.0
+    t[2] = (0.5, 0.25, -0.75, 1.0)[k]
+    return t
+
+
+def _step_mask(c, B, h, w):
+    m = torch.rand(B, 1, h, w, generator=c.g)
+    flat = m.view(B, -1)
+    flat[:, 0::4] = 1.0
+    flat[:, 1::4] = 0.0                                   # ones, zeros and fractions in every float4
+    return c.put(m.view(B, h * w)).view(B, 1, h, w)          # rows of hw elements: the margins are 256 whole rows, as the layout describes the mask
+
+
+def _steps(kind, nv, *, pag_rng=False):
+    """Every form of one step launcher at one size: two-forward + rescale, three-forward, three-forward + rescale, each without and with a mixed mask,
+    each at the step indices 0, 1 and last."""
+    ch, h, w = STEP_SHAPES[nv]
+    shape = (3, ch, h, w)
+
+    def run(c):
+        rec = c.rec
+        coef = _step_coef(c)
+        eu, em, ec, ep = (c.put(_step_eps(c, shape, k)) for k in range(4))
+        mask, known, noise = _step_mask(c, 3, h, w), c.f(*shape), c.f(*shape)
+        rng = c.put(_i32(STEP_RNG)) if kind == "stochastic" or pag_rng else None
+        for img, rs in ((None, RESCALE), (em, 0.0), (em, RESCALE)):
+            for blend in ({}, dict(mask=mask, known=known, noise=noise)):
+                for idx in (0, 1, STEP_ROWS - 1):
+                    x, xp, st = c.f(*shape), c.f(*shape), _state(c, idx, STEP_ROWS)
+                    if kind == "guided":
+                        rec.cfg_dpm_step_guided(eu, img, ec, x, xp, coef, st, G_TEXT, G_IMAGE, rs, **blend)
+                    elif kind == "stochastic":
+                        rec.cfg_dpm_step_stochastic(eu, img, ec, x, xp, coef, st, rng, G_TEXT, G_IMAGE, rs, **blend)
+                    else:
+                        rec.cfg_dpm_step_pag(eu, img, ec, ep, x, xp, coef, st, G_TEXT, G_IMAGE, G_PAG, rs, rng=rng, **blend)
+    return run
+
+
+for _nv in STEP_SHAPES:
+    add(f"step-guided-nv{_nv}", _steps("guided", _nv))
+    add(f"step-stochastic-nv{_nv}", _steps("stochastic", _nv))
+    add(f"step-pag-nv{_nv}", _steps("pag", _nv))
+    add(f"step-pag-rng-nv{_nv}", _steps("pag", _nv, pag_rng=True))
+
+
+def _step_substitutions(c):
+    """The launcher's own substitutions, on inputs that are all NaN where they must not be read: eps_perturbed with g_pag = 0 is the guided launch (its
+    outputs must have that launch's bits: ``same_bits``), eps_image at g_image == g_text the two-forward one."""
+    ch, h, w = STEP_SHAPES[36]
+    shape = (3, ch, h, w)
+    rec = c.rec
+    coef, st = _step_coef(c), _state(c, 1, STEP_ROWS)
+    eu, em, ec = (c.put(_step_eps(c, shape, k)) for k in range(3))
+    unread = c.put(torch.full(shape, float("nan")))
+    x, xp = c.randn(*shape), c.randn(*shape)
+    outs = []
+    for launch in (lambda a, b: rec.cfg_dpm_step_guided(eu, em, ec, a, b, coef, st, G_TEXT, G_IMAGE, RESCALE),
+                   lambda a, b: rec.cfg_dpm_step_pag(eu, em, ec, unread, a, b, coef, st, G_TEXT, G_IMAGE, 0.0, RESCALE),
+                   lambda a, b: rec.cfg_dpm_step_guided(eu, None, ec, a, b, coef, st, G_TEXT, None, RESCALE),
+                   lambda a, b: rec.cfg_dpm_step_guided(eu, unread, ec, a, b, coef, st, G_TEXT, G_TEXT, RESCALE)):
+        a, b = c.put(x.clone()), c.put(xp.clone())
+        launch(a, b)
+        outs.append((a, b))
+    rec.same_bits = [(outs[0][0], outs[1][0]), (outs[0][1], outs[1][1]), (outs[2][0], outs[3][0]), (outs[2][1], outs[3][1])]
+
+
+add("step-substitutions-unread-inputs-are-nan", _step_substitutions)
+
+
+def _product_steps(B, S):
+    def run(c):
+        shape = (B, 4, S, S)
+        coef, st = _step_coef(c), _state(c, 1, STEP_ROWS)
+        eu, em, ec, ep = (c.f(*shape) for _ in range(4))
+        blend = dict(mask=_step_mask(c, B, S, S), known=c.f(*shape), noise=c.f(*shape))
+        rng = c.put(_i32(STEP_RNG))
+        c.rec.cfg_dpm_step_guided(eu, em, ec, c.f(*shape), c.f(*shape), coef, st, G_TEXT, G_IMAGE, RESCALE, **blend)
+        c.rec.cfg_dpm_step_stochastic(eu, em, ec, c.f(*shape), c.f(*shape), coef, st, rng, G_TEXT, G_IMAGE, RESCALE, **blend)
+        c.rec.cfg_dpm_step_pag(eu, em, ec, ep, c.f(*shape), c.f(*shape), coef, st, G_TEXT, G_IMAGE, G_PAG, RESCALE, rng=rng, **blend)
+    return run
+
+
+add("product-steps-16x4x64x64", _product_steps(16, 64))
+add("product-steps-4x4x96x96", _product_steps(4, 96))
+
+
+def _fusion_draw(c):
+    n = 16
+    forced = torch.full((n,), -1.0)
+    forced[:4] = torch.tensor([0.0, 0.29, 0.5, 0.99])
+    for state, only_last, fo in ((None, 0, None), ((STEP_ROWS - 1, STEP_ROWS), 1, forced), ((1, STEP_ROWS), 1, None)):
+        c.rec.fusion_draw(None if state is None else _state(c, *state), c.put(_i32(STEP_RNG)), None if fo is None else c.put(fo), c.out_flat(n, 2),
+                          n_layers=n, rule1=0.3, rule2=0.7, scale=2.0, only_last_step=only_last)
+
+
+add("fusion-draw-16-layers", _fusion_draw)
+
+
+# ============================================================================================================================== FreeU
+def _freeu(c, B, h, w, cx, cs, *, b=1.5, s=0.2, sliced=False, flat_channels=False):
+    """One pv_freeu_rows launch on strided inputs AND outputs (``Recorder.freeu`` always hands out contiguous outputs: the launch is recorded directly).
+    ``sliced``: both inputs are column slices of one wider buffer.  ``flat_channels``: channel 0 of the skip is constant, channel 1 zero."""
+    rows = B * h * w
+    xs = c.randn(rows, max(cx, 1)) if cx else None
+    sk = c.randn(rows, max(cs, 1)) + 0.5 if cs else None
+    if flat_channels and cs:
+        sk[:, 0], sk[:, 1] = 3.25, 0.0
+    if sliced:
+        buf = c.put(torch.cat([xs, sk], 1).to(F16), cx + cs + 8)
+        x, skip = buf[:, :cx], buf[:, cx:]
+    else:
+        x = c.put(xs.to(F16), cx + 8) if cx else None
+        skip = c.put(sk.to(F16), cs + 16) if cs else None
+    xo = c.out(rows, cx, gap=24) if cx else None
+    so = c.out(rows, cs, gap=8) if cs else None
+    p = lambda t: t.data_ptr() if t is not None else None
+    ld = lambda t: t.stride(0) if t is not None else 0
+    c.rec._add(c.rec.lib.pv_freeu_rows, p(x), ld(x), cx, p(xo), ld(xo), float(b), p(skip), ld(skip), cs, p(so), ld(so), float(s), B, h, w, tag=("freeu_rows_kernel", 0.0, 0.0))
+
+
+add("freeu-skip-cs8-2x2", lambda c: _freeu(c, 2, 2, 2, 0, 8, s=0.9))
+add("freeu-skip-cs136-5x7", lambda c: _freeu(c, 2, 5, 7, 0, 136, s=0.2))                     # a second channel group with one live chunk; 35 pixels on 16 lanes
+add("freeu-skip-cs16-4x6-constant-and-zero-channel", lambda c: _freeu(c, 2, 4, 6, 0, 16, s=2.0, flat_channels=True))      # even h: y = h / 2 is exact
+add("freeu-x-cx16-2x2", lambda c: _freeu(c, 1, 2, 2, 16, 0))
+add("freeu-x-cx48-5x7", lambda c: _freeu(c, 2, 5, 7, 48, 0, b=1.6))                            # 420 chunks: a second block, partly live
+add("freeu-both-cx48-cs136-5x7", lambda c: _freeu(c, 2, 5, 7, 48, 136, b=1.5, s=0.9))
+add("freeu-both-sliced-cx16-cs24-4x6", lambda c: _freeu(c, 2, 4, 6, 16, 24, sliced=True, flat_channels=True))
+
+
+def _product_freeu(h, cs, b, s):
+    def run(c):
+        rows = 2 * h * h
+        c.rec.freeu(c.put(c.randn(rows, 1280).to(F16)), c.put((c.randn(rows, cs) + 0.5).to(F16)), batch=2, h=h, w=h, b=b, s=s)
+    return run
+
+
+# the FreeU blocks of the SD-1.5 UNet (unet.UNetEngine: up block 0 at 8 x 8 pops three 1280-wide skips, up block 1 at 16 x 16 two of 1280 and one of 640)
+add("product-freeu-8x8-c1280-skip1280", _product_freeu(8, 1280, 1.5, 0.9))
+add("product-freeu-16x16-c1280-skip1280", _product_freeu(16, 1280, 1.6, 0.2))
+add("product-freeu-16x16-c1280-skip640", _product_freeu(16, 640, 1.6, 0.2))
+
+
+# ============================================================================================================================== resize / fp32 pointwise
+def _resize(c, B, ch, h, w, oh, ow, *, ca=True, y=True, y_shift=False):
+    x = c.f(B, ch, h, w)
+    cav = c.put(torch.linspace(0.6, 1.4, B)) if ca else None           # a different ca[b] per sample
+    yv = cbv = None
+    if y:
+        if y_shift:                                                   # ow % 4 == 0, y 4 bytes off a 16-byte boundary: the scalar kernel
+            yv = c.f(B * ch * oh * ow + 1)[1:].view(B, ch, oh, ow)
+            assert yv.data_ptr() % 16 == 4
+        else:
+            yv = c.f(B, ch, oh, ow)
+        cbv = c.put(torch.linspace(-0.5, 0.7, B))
+    c.rec.resize_bilinear_affine(x, (oh, ow), cav, yv, cbv, out=c.out_flat(B, ch, oh, ow))
+
+
+add("resize-1x1-to-4x4", lambda c: (_resize(c, 2, 1, 1, 1, 4, 4), _resize(c, 2, 1, 1, 1, 4, 4, ca=False, y=False)))
+add("resize-3x5-to-7x4-scalar", lambda c: (_resize(c, 2, 3, 3, 5, 7, 4), _resize(c, 2, 3, 3, 5, 7, 4, ca=False), _resize(c, 2, 3, 3, 5, 7, 4, y=False)))
+add("resize-4x4-to-6x8-vector", lambda c: (_resize(c, 2, 3, 4, 4, 6, 8), _resize(c, 2, 3, 4, 4, 6, 8, ca=False, y=False), _resize(c, 2, 3, 4, 4, 6, 8, y=False)))
+add("resize-8x8-identity", lambda c: (_resize(c, 2, 4, 8, 8, 8, 8, ca=False, y=False), _resize(c, 2, 4, 8, 8, 8, 8)))
+add("resize-4x4-to-6x8-y-off-alignment", lambda c: _resize(c, 2, 3, 4, 4, 6, 8, y_shift=True))
+add("product-resize-64-to-96", lambda c: _resize(c, 4, 4, 64, 64, 96, 96))
+
+
+def _composite(c, h, w, alias):
+    B, ch = 2, 3
+    m = torch.rand(B, 1, h, w, generator=c.g)
+    m.view(B, -1)[:, 0], m.view(B, -1)[:, 1] = 1.0, 0.0
+    gen = c.f(B, ch, h, w, scale=1.5)
+    c.rec.composite_clamp(gen, c.f(B, ch, h, w, scale=1.5), c.put(m), -1.0, 1.0, out=gen if alias else c.out_flat(B, ch, h, w))
+
+
+add("composite-clamp-2x2", lambda c: _composite(c, 2, 2, False))
+add("composite-clamp-6x6", lambda c: _composite(c, 6, 6, False))
+add("composite-clamp-6x6-out-is-gen", lambda c: _composite(c, 6, 6, True))
+for _n in (1, 35):
+    add(f"clamp-n{_n}", lambda c, n=_n: c.rec.clamp_(c.f(2, 1, n, scale=2.0), -1.0, 1.0))
+    add(f"affine-rows-n{_n}", lambda c, n=_n: (c.rec.affine_rows(c.f(2, 1, n), c.put(torch.tensor([0.7, -1.3])), out=c.out_flat(2, 1, n)),
+                                               c.rec.affine_rows(c.f(2, 1, n), c.put(torch.tensor([0.7, -1.3])), c.f(2, 1, n), c.put(torch.tensor([0.4, 2.0])),
+                                                                 out=c.out_flat(2, 1, n))))
+
+
+# ============================================================================================================================== conditioning front ends
+def _rows_mean(c, cols, count, group_rows, accumulate, groups=3):
+    x = c.h((groups - 1) * group_rows + count, cols)
+    y = c.h(groups, cols) if accumulate else c.out(groups, cols)
+    c.rec.rows_mean(x, groups=groups, count=count, group_rows=group_rows, out=y, accumulate=accumulate)
+
+
+add("rows-mean-cols8-count1", lambda c: _rows_mean(c, 8, 1, 1, False))
+add("rows-mean-cols264-count9-gap-accumulate", lambda c: _rows_mean(c, 264, 9, 12, True))      # 33 chunks: a second block per group with one live chunk
+add("rows-mean-cols8-count257-gap", lambda c: _rows_mean(c, 8, 257, 258, False))
+add("rows-mean-cols264-count257-accumulate", lambda c: _rows_mean(c, 264, 257, 257, True))
+
+#: fp32 values around every edge of the fp16 grid: the overflow threshold 65520 (the first value that rounds to infinity) and its neighbours, the
+#: largest finite value, ties at the subnormal spacing 2^-24 (half of it rounds to even = 0), signed zeros, infinities
+CAST_VALUES = (65520.0, 65519.996, 65504.0, 65536.0, -65520.0, 1e10, -7e4, 2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * 1.0001, 3 * 2.0 ** -25, -(2.0 ** -24), 2.0 ** -14,
+               2.0 ** -14 - 2.0 ** -25, 0.0, -0.0, float("inf"), float("-inf"), 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, 0.1, -0.3)
+
+
+def _casts(c):
+    sp = torch.tensor(CAST_VALUES)
+    wide = torch.cat([sp, c.randn(257 - sp.numel()) * 100.0])
+    for t in (torch.tensor([65520.0]), wide):
+        c.rec.cast_to_f16(c.put(t), out=c.out_flat(t.numel(), dtype=F16))
+    h16 = torch.cat([sp.to(F16), c.randn(257 - sp.numel()).to(F16)])
+    for t in (torch.tensor([-0.0], dtype=F16), h16):
+        c.rec.cast_to_f32(c.put(t), out=c.out_flat(t.numel(), dtype=F32))
+
+
+add("casts-n1-n257-grid-edges", _casts)
+add("patchify-28px-patch14-kpad640", lambda c: c.rec.patchify(c.f(2, 3, 28, 28), batch=2, ch=3, img=28, patch=14, kpad=640))
+add("clip-vision-embed-ntok5-dim8", lambda c: c.rec.clip_vision_embed(c.put(c.randn(2 * 4, 8).to(F16)), c.f(8), c.put(c.randn(5, 8)), batch=2, ntok=5, dim=8))
+
+
+def _text_embed(c):
+    B, S, dim, vocab = 2, 77, 8, 11
+    tok, pos = c.put(c.randn(vocab, dim)), c.put(c.randn(S, dim))
+    for E in (0, 1, 2):
+        ids = torch.randint(0, vocab, (B, S), generator=c.g)
+        ids[0, 1], ids[1, S - 1], ids[1, 3] = 0, 10, 10
+        con = c.put(c.randn(B * E, dim).to(F16)) if E else None
+        pidx = c.put(torch.tensor([0, S - E], dtype=torch.int64)) if E else None      # the placeholder at position 0 and at the last one that fits
+        c.rec.clip_text_embed(c.put(ids), tok, pos, con, pidx, n_concept=E, batch=B, seq=S, dim=dim)
+
+
+add("clip-text-embed-seq77-concepts-0-1-2", _text_embed)
 
 
 #: Instantiations no argument and no per-call switch can select: the only symbols the dispatch sweep may leave unaudited

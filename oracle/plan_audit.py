@@ -173,7 +173,12 @@ def _flags(name, p) -> str:
         if p.act:
             f.append(f"act={p.act}")
         return " ".join(f)
-    keys = {"pv_attention": ("causal", "lse"), "pv_cross_attention": ("vnorm", "fusion"), "pv_cross_attention_lnq": ("ln", "vnorm", "fusion"),
+    if name in ("pv_cfg_dpm_step_guided", "pv_cfg_dpm_step_stochastic", "pv_cfg_dpm_step_pag"):
+        three, pag = A.step_reads(p)
+        return " ".join(k for k, c in (("three-forward", three), ("pag", pag), ("rescale", p.rescale > 0), ("mask", g("mask")), ("rng", g("rng"))) if c)
+    keys = {"pv_freeu_rows": ("x", "skip"), "pv_resize_bilinear_affine_f32": ("ca", "y"), "pv_affine_rows_f32": ("y",), "pv_rows_mean": ("accumulate",),
+            "pv_clip_text_embed": ("n_concept",),
+            "pv_attention": ("causal", "lse"), "pv_cross_attention": ("vnorm", "fusion"), "pv_cross_attention_lnq": ("ln", "vnorm", "fusion"),
             "pv_cross_attention_fused": ("ln", "fusion"), "pv_row_gemm": ("ln", "geglu", "x_norm"), "pv_groupnorm_apply": ("act",),
             "pv_layernorm": ("act",)}.get(name, ())
     f = [k for k in keys if g(k)]
@@ -226,20 +231,18 @@ class Auditor:
                 return
             v[k], base[k] = make_view(pool, addr, buf, f"{where}, field {k}")
 
-        # fields whose extent depends on device state (the step index) are resolved after the state
-        cfg = name in ("pv_cfg_dpm_step", "pv_cfg_dpm_step_masked")
-        if (name == "pv_timestep_embedding" or cfg) and L.get("state") is not None:
-            resolve("state", L["state"])
-            idx = A.step_index(v["state"]) if "state" in v else 0
-            if name == "pv_timestep_embedding":
-                L["timesteps"] = A.Buf(A.F32, 1, idx + 1, 0)
-            if cfg:
-                L["coef"] = A.Buf(A.F32, 1, (idx + 1) * 8, 0)
+        # a field whose extent depends on device contents (the step index, the token ids) is resolved after the buffer that holds them (A.DEPENDENT)
+        dep = A.DEPENDENT.get(name)
+        if dep is not None and L.get(dep[0]) is not None:
+            first_k, dep_k, extent, row = dep
+            resolve(first_k, L[first_k])
+            if first_k in v:
+                L[dep_k] = extent(p, v[first_k])
         for k, buf in L.items():
             if k not in v and buf is not None:
                 resolve(k, buf)
-        if cfg:
-            v["coef"] = v["coef"][:, A.step_index(v["state"]) * 8:][:, :8]
+        if dep is not None and dep[3] and dep[1] in v:
+            v[dep[1]] = v[dep[1]][:, A.step_index(v[dep[0]]) * dep[3]:][:, :dep[3]]
         if name == "pv_cross_attention_fused" and p.kimg not in self.kv:
             raise AuditError(f"{where}: kimg {p.kimg:#x} was not built by an audited pv_xattn_pack_kv")
 

@@ -1,6 +1,8 @@
 """CPU checks of ``oracle.abi_ref`` (the per-launch references of the plan audit) and of the audit's comparator: each reference against an
-independent formulation (``F.conv2d`` / ``F.linear`` / ``F.scaled_dot_product_attention``), the comparator against injected defects, and the
-field coverage of the ctypes parameter structs."""
+independent formulation (``F.conv2d`` / ``F.linear`` / ``F.scaled_dot_product_attention``; for the launchers of the newer loop features and the
+conditioning plans ``F.interpolate``, ``torch.fft``, the kernel tests' restatements, ``Tensor.half``, ``F.embedding``, at the inputs of the edge
+catalogue), the comparator against injected defects, the derived bounds against the kernel tests' tolerances, the field / argument coverage of the
+ABI, and the partition of its functions into audited and deliberately not audited ones."""
 import math
 import os
 import sys
@@ -399,14 +401,49 @@ def test_every_abi_field_is_modelled_or_listed(struct):
     assert listed <= fields
 
 
-def test_every_recorded_launcher_has_a_reference():
-    """The launchers the inference plans record (ops.Recorder's forward methods) all have a layout and a reference."""
-    assert set(A.LAYOUT) == set(A.REF)
-    for name in ("pv_gemm_conv", "pv_attention", "pv_cross_attention", "pv_cross_attention_fused", "pv_cross_attention_lnq", "pv_xattn_pack_kv",
+#: the launchers the audit covered before the partition existed: none of them may leave ``REF``
+FIRST_AUDITED = ("pv_gemm_conv", "pv_attention", "pv_cross_attention", "pv_cross_attention_fused", "pv_cross_attention_lnq", "pv_xattn_pack_kv",
                  "pv_row_gemm", "pv_layernorm", "pv_groupnorm_stats", "pv_groupnorm_stats_from_colstats", "pv_groupnorm_scale_shift",
                  "pv_groupnorm_apply", "pv_im2col3x3", "pv_conv_out", "pv_timestep_embedding", "pv_cfg_dpm_step", "pv_step_advance",
-                 "pv_pointwise_nchw", "pv_softmax_rows", "pv_posterior_sample", "pv_cfg_dpm_step_masked"):
+                 "pv_pointwise_nchw", "pv_softmax_rows", "pv_posterior_sample", "pv_cfg_dpm_step_masked")
+#: modules whose recorders are the plans of ``run_inference`` / ``generate.py`` (no backward pass lives in them)
+INFERENCE_MODULES = ("infer", "pipeline", "unet", "clip", "vae", "scheduler")
+
+
+def _inference_launchers():
+    """Launchers the inference modules can record: the ``ops.Recorder`` methods they call on a recorder (``rec.<m>(`` / ``.tail.<m>(``), and the ``pv_*``
+    functions those methods add."""
+    import importlib
+    import inspect
+    import re
+    from photoverse_amd.ops import Recorder
+    adds = {m: set(re.findall(r"_add\(\s*self\.lib\.(pv_\w+)", inspect.getsource(f))) for m, f in inspect.getmembers(Recorder, inspect.isfunction)}
+    found = set()
+    for mod in INFERENCE_MODULES:
+        src = inspect.getsource(importlib.import_module(f"photoverse_amd.{mod}"))
+        for m in re.findall(r"(?:rec|tail)\.(\w+)\(", src):
+            found |= adds.get(m, set())
+    return found
+
+
+def test_every_recorded_launcher_has_a_reference():
+    """Every function of the C ABI (``_lib.SIGNATURES``) is in exactly one of ``REF`` (audited) and ``NOT_AUDITED`` (outside the audit, with its reason):
+    a new ``pv_*`` function fails here until someone places it.  Nothing an inference plan can record is outside the audit."""
+    from photoverse_amd import _lib
+    assert set(A.LAYOUT) == set(A.REF)
+    names = set(_lib.SIGNATURES)
+    assert not (set(A.REF) & set(A.NOT_AUDITED)), set(A.REF) & set(A.NOT_AUDITED)
+    assert not (names - set(A.REF) - set(A.NOT_AUDITED)), f"launchers neither audited nor listed as outside the audit: {names - set(A.REF) - set(A.NOT_AUDITED)}"
+    assert not ((set(A.REF) | set(A.NOT_AUDITED)) - names), f"placed, but not in the ABI: {(set(A.REF) | set(A.NOT_AUDITED)) - names}"
+    assert all(isinstance(r, str) and r.strip() for r in A.NOT_AUDITED.values())
+    for name in FIRST_AUDITED:
         assert name in A.REF, name
+    inference = _inference_launchers()
+    assert {"pv_cfg_dpm_step_pag", "pv_freeu_rows", "pv_clip_text_embed", "pv_fusion_draw", "pv_composite_clamp_f32"} <= inference, inference
+    assert not (inference & set(A.NOT_AUDITED)), f"recorded by an inference plan, listed as outside the audit: {inference & set(A.NOT_AUDITED)}"
+    # every launcher with a state- or content-dependent extent names two of its own arguments
+    for name, (first, dep, _, _) in A.DEPENDENT.items():
+        assert name in A.REF and {first, dep} <= set(A.ARGS[name]), name
 
 
 # ------------------------------------------------------------------------------------------------------------------ comparator on attention
@@ -463,3 +500,235 @@ def test_comparator_catches_defects_in_attention_outputs(attn_expects, launcher,
         y[64:80] = e.ref[64:80] * 1.05
     fails, _, _ = PA.compare(exp, {"out": y})
     assert [f for f in fails if "bound (" in f], fails
+
+
+# ------------------------------------------------------------------------------------------------------------------ guided / conditioning launchers
+NEW_LAUNCHERS = sorted(A.ARG_FUNCS)
+NEW_CASES = ("step-", "product-", "fusion-", "freeu-", "resize-", "composite-", "clamp-", "affine-", "rows-mean", "casts-", "patchify", "clip-")
+
+
+@pytest.fixture(scope="module")
+def catalogue(lib):
+    """launcher -> [(case, call, params, views, expects)]: the references of the launchers above on the inputs of the edge catalogue, recorded dry."""
+    from oracle import edge_cases as E
+    out = {n: [] for n in NEW_LAUNCHERS}
+    for c in E.CASES:
+        if not c.name.startswith(NEW_CASES):
+            continue
+        with E.environment(c.env):
+            rec = E.build(c, "cpu")
+        for i, (fn, _) in enumerate(rec.calls):
+            name, p, v = E.host_views(rec, i)
+            out[name].append((c.name, i, p, v, A.REF[name](p, v)))
+    return out
+
+
+def same(a, b, tol=1e-12):
+    assert a.shape == b.shape, (a.shape, b.shape)
+    fin = torch.isfinite(b)
+    assert torch.equal(a[~fin], b[~fin].to(a.dtype))
+    err = ((a[fin] - b[fin]).abs() / (1 + b[fin].abs())).max().item() if fin.any() else 0.0
+    assert err < tol, err
+
+
+def _r32(x):
+    return torch.tensor(float(x), dtype=torch.float32).item()
+
+
+def _indep_step(p, v):
+    """tests/test_pag_cpu.py's restatement (it contains those of test_guidance_cpu.py and test_sampler_cpu.py) with the noise of oracle.philox."""
+    from oracle.philox import noise_ref
+    from test_pag_cpu import pag_step_ref
+    B, shape = p.batch, (p.batch, p.channels, p.hw)
+    t = lambda k: v[k].reshape(shape) if k in v else None
+    z = None
+    if "rng" in v:
+        w = [int(x) & 0xFFFFFFFF for x in v["rng"].reshape(-1).tolist()]
+        st = v["state"].reshape(-1).tolist()
+        z = noise_ref(shape, w[0] | (w[1] << 32), w[2], w[3], min(st[0], st[1] - 1))
+    blend = dict(mask=v["mask"].reshape(B, 1, p.hw), known=t("known"), noise=t("noise")) if "mask" in v else {}
+    xn, x0, _ = pag_step_ref(t("eps_uncond"), t("eps_image"), t("eps_cond"), t("eps_perturbed"), t("latents"), t("x0_prev"), v["coef"].reshape(-1),
+                             _r32(p.g_text), _r32(p.g_image), _r32(getattr(p, "g_pag", 0.0)), _r32(p.rescale), z=z, **blend)
+    return {"latents": xn.reshape(1, -1), "x0_prev": x0.reshape(1, -1)}
+
+
+def _indep_fusion(p, v):
+    from oracle.philox import philox4x32_10
+    w = [int(x) & 0xFFFFFFFF for x in v["rng"].reshape(-1).tolist()]
+    on = not (p.only_last_step and "state" in v) or v["state"][0, 0].item() == v["state"][0, 1].item() - 1
+    out = torch.ones(p.n_layers, 2, dtype=D)
+    for i in range(p.n_layers):
+        u = (int(philox4x32_10((w[0], w[1]), (w[2], i, 0, 0))[0]) >> 8) / 2.0 ** 24
+        if "forced" in v and v["forced"][0, i] >= 0:
+            u = v["forced"][0, i].item()
+        if on and u < _r32(p.rule1):
+            out[i] = torch.tensor([_r32(p.scale), 0.0])
+        elif on and u > _r32(p.rule2):
+            out[i] = torch.tensor([0.0, _r32(p.scale)])
+    nxt = v["rng"].reshape(-1).clone()
+    nxt[2] += 1                                                     # int32: wraps like the device's uint32 word
+    return {"out": out, "rng": nxt.double().reshape(1, 4)}
+
+
+def _indep_freeu(p, v):
+    from test_freeu_cpu import fourier_filter_ref
+    res = {}
+    if "x" in v:
+        scale = torch.ones(p.cx, dtype=D)
+        scale[:p.cx // 2] = _r32(p.b)
+        res["x_out"] = v["x"].double() * scale
+    if "skip" in v:
+        planes = v["skip"].double().reshape(p.batch, p.h, p.w, p.cs).permute(0, 3, 1, 2)
+        res["skip_out"] = fourier_filter_ref(planes, 1, _r32(p.s)).permute(0, 2, 3, 1).reshape(-1, p.cs)
+    return res
+
+
+def _indep_resize(p, v):
+    B, C_ = p.batch, p.channels
+    r = F.interpolate(v["x"].double().reshape(B, C_, p.h, p.w), size=(p.oh, p.ow), mode="bilinear", align_corners=False)
+    if "ca" in v:
+        r = r * v["ca"].double().reshape(B, 1, 1, 1)
+    if "y" in v:
+        r = r + v["cb"].double().reshape(B, 1, 1, 1) * v["y"].double().reshape(B, C_, p.oh, p.ow)
+    return {"out": r.reshape(1, -1)}
+
+
+def _indep_text(p, v):
+    B, S, E = p.batch, p.seq, p.n_concept
+    rows = []
+    for b in range(B):
+        emb = F.embedding(v["ids"][b].long(), v["tok"].double())                  # nn.Embedding's arithmetic
+        if E:
+            i = int(v["placeholder_idx"][0, b])
+            emb = torch.cat([emb[:i], v["concept"].double().reshape(B, E, p.dim)[b], emb[i + 1:]])[:S]      # models/clip.py: insert, shift, truncate
+        rows.append(emb + F.embedding(torch.arange(S), v["pos"].double()))
+    return {"out": torch.cat(rows)}
+
+
+def _indep_small(name, p, v):
+    d = lambda k: v[k].double()
+    if name == "pv_affine_rows_f32":
+        r = torch.einsum("b,bi->bi", d("ca").reshape(-1), d("x").reshape(p.batch, -1))
+        if "y" in v:
+            r = torch.addcmul(r, d("cb").reshape(-1, 1), d("y").reshape(p.batch, -1))
+        return {"out": r.reshape(1, -1)}
+    if name == "pv_composite_clamp_f32":
+        m = d("mask").reshape(p.batch, 1, p.hw)
+        g, o = d("gen").reshape(p.batch, p.channels, p.hw), d("orig").reshape(p.batch, p.channels, p.hw)
+        return {"out": torch.minimum(torch.maximum(o + m * (g - o), torch.tensor(_r32(p.lo), dtype=D)), torch.tensor(_r32(p.hi), dtype=D)).reshape(1, -1)}
+    if name == "pv_clamp_f32":
+        return {"x": torch.minimum(torch.maximum(d("x"), torch.tensor(_r32(p.lo), dtype=D)), torch.tensor(_r32(p.hi), dtype=D))}
+    if name == "pv_rows_mean":
+        out = torch.stack([d("x")[g * p.group_rows:g * p.group_rows + p.count].sum(0) / p.count for g in range(p.groups)])
+        return {"y": out + (d("y") if p.accumulate else 0)}
+    if name == "pv_cast_f32_to_f16":
+        return {"y": v["x"].half().double()}
+    if name == "pv_cast_f16_to_f32":
+        return {"y": v["x"].float().double()}
+    if name == "pv_patchify":
+        g = p.img // p.patch
+        cols = F.unfold(d("x").reshape(p.batch, p.ch, p.img, p.img), p.patch, stride=p.patch).transpose(1, 2).reshape(p.batch * g * g, -1)
+        return {"out": F.pad(cols.half().double(), (0, p.kpad - cols.shape[1]))}
+    if name == "pv_clip_vision_embed":
+        tokens = torch.cat([d("cls").reshape(1, 1, p.dim).expand(p.batch, 1, p.dim), d("patches").reshape(p.batch, p.ntok - 1, p.dim)], 1)
+        return {"out": (tokens + F.embedding(torch.arange(p.ntok), d("pos"))).reshape(-1, p.dim)}
+    raise KeyError(name)
+
+
+def independent(name, p, v):
+    if name.startswith("pv_cfg_dpm_step"):
+        return _indep_step(p, v)
+    return {"pv_fusion_draw": _indep_fusion, "pv_freeu_rows": _indep_freeu, "pv_resize_bilinear_affine_f32": _indep_resize,
+            "pv_clip_text_embed": _indep_text}.get(name, lambda p_, v_: _indep_small(name, p_, v_))(p, v)
+
+
+@pytest.mark.parametrize("launcher", NEW_LAUNCHERS)
+def test_reference_matches_an_independent_evaluation(catalogue, launcher):
+    """Each reference against another formulation of the same operation at every launch of the catalogue: F.interpolate (resize), torch.fft (FreeU),
+    the kernel tests' restatements (steps), Tensor.half (casts), F.embedding / F.unfold (embeds, patchify): equal to fp64 rounding."""
+    entries = catalogue[launcher]
+    assert entries, launcher
+    for case, i, p, v, exp in entries:
+        ind = independent(launcher, p, v)
+        assert set(ind) <= set(exp), (case, set(ind), set(exp))
+        for k, t in ind.items():
+            # the FreeU closed form sums seven terms where the FFT transforms the plane: both within 1e-11 of the exact filter
+            same(exp[k].ref, t, 1e-11 if launcher == "pv_freeu_rows" else 1e-12)
+
+
+def _as_stored(exp, v):
+    return {k: e.ref.to(v[k].dtype) for k, e in exp.items() if e.derive is None}
+
+
+@pytest.mark.parametrize("launcher", NEW_LAUNCHERS)
+def test_comparator_accepts_the_rounded_reference_and_rejects_twice_the_bound(catalogue, launcher):
+    for case, i, p, v, exp in catalogue[launcher]:
+        got = _as_stored(exp, v)
+        assert not PA.compare(exp, got)[0], (case, i, PA.compare(exp, got)[0])
+        for k, e in exp.items():
+            if e.derive is not None:
+                continue
+            bad = {kk: t.clone() for kk, t in got.items()}
+            fin = torch.isfinite(e.ref)
+            j = int(torch.where(fin, -e.ref.abs(), torch.full_like(e.ref, -float("inf"))).argmax())      # the smallest finite reference: the move is not absorbed
+            r, c = divmod(j, e.ref.shape[1])
+            step = 1.0 if e.store is None else 2 * e.bound[r, c].item()
+            bad[k][r, c] = (e.ref[r, c] + step).to(bad[k].dtype) if fin.any() else 0.0       # (a reference of infinities only: a finite value is wrong)
+            assert PA.compare(exp, bad)[0], (case, i, k, "an element moved by twice its bound passes")
+
+
+def test_step_bounds_are_no_looser_than_the_kernel_tests(catalogue):
+    """At the catalogue's inputs every derived element bound of the three step launchers is within what tests/test_guidance_gpu.py, test_sampler_gpu.py
+    and test_pag_gpu.py allow: TOL_STEP / TOL_RESCALE in (1 + |ref|) form, plus TOL_NOISE |cn| on the latents of a stochastic launch."""
+    import test_guidance_gpu as G
+    import test_sampler_gpu as S
+    assert A.TOL_NOISE == S.TOL_NOISE and (S.TOL_STEP, S.TOL_RESCALE) == (G.TOL_STEP, G.TOL_RESCALE)
+    n = 0
+    for launcher in ("pv_cfg_dpm_step_guided", "pv_cfg_dpm_step_stochastic", "pv_cfg_dpm_step_pag"):
+        for case, i, p, v, exp in catalogue[launcher]:
+            tol = G.TOL_RESCALE if p.rescale > 0 else G.TOL_STEP
+            cn = abs(v["coef"][0, 7].item()) if "rng" in v else 0.0
+            for k, extra in (("latents", S.TOL_NOISE * cn), ("x0_prev", 0.0)):
+                e = exp[k]
+                worst = (e.bound / (tol * (1 + e.ref.abs()) + extra)).max().item()
+                assert worst <= 1.0, (case, i, k, worst)
+                n += 1
+    assert n >= 2 * 18 * 16
+
+
+def test_freeu_and_resize_bounds_are_no_looser_than_the_kernel_tests(catalogue):
+    """FreeU's skip: 2^-10 |ref| + 2^-12 max|x| (1 + |s - 1|) (tests/test_freeu_gpu.py); the resize: rtol = atol = 1e-5 (tests/test_hires_gpu.py)."""
+    n = 0
+    for case, i, p, v, exp in catalogue["pv_freeu_rows"]:
+        if "skip_out" in exp:
+            e, s = exp["skip_out"], _r32(p.s)
+            allowed = 2.0 ** -10 * e.ref.abs() + 2.0 ** -12 * v["skip"].double().abs().max() * (1 + abs(s - 1))
+            assert (e.bound <= allowed).all(), (case, (e.bound / allowed).max().item())
+            n += 1
+    for case, i, p, v, exp in catalogue["pv_resize_bilinear_affine_f32"]:
+        e = exp["out"]
+        assert (e.bound <= 1e-5 * (1 + e.ref.abs())).all(), (case, (e.bound / (1e-5 * (1 + e.ref.abs()))).max().item())
+        n += 1
+    assert n >= 8 + 12
+
+
+def test_the_identity_resize_and_the_zero_weight_taps_are_exact(catalogue):
+    ident = [(p, v, exp) for case, i, p, v, exp in catalogue["pv_resize_bilinear_affine_f32"] if (p.h, p.w) == (p.oh, p.ow) and "ca" not in v and "y" not in v]
+    assert ident
+    for p, v, exp in ident:
+        assert torch.equal(exp["out"].ref, v["x"].double())
+    # a weight of exactly 0 returns the tap itself, whatever its neighbour holds
+    x = torch.tensor([[1.0, float("inf")], [2.0, float("nan")]]).reshape(1, -1)
+    p = SimpleNamespace(batch=1, channels=1, h=2, w=2, oh=2, ow=2, ca=0, y=0, cb=0)
+    assert torch.equal(A.ref_resize(p, dict(x=x))["out"].ref.nan_to_num(nan=-7.0), x.double().nan_to_num(nan=-7.0))
+
+
+@pytest.mark.parametrize("launcher", NEW_LAUNCHERS)
+def test_every_positional_argument_is_modelled(launcher, monkeypatch):
+    """Every name of ``ARGS[launcher]`` is read by its layout or its reference, and ``ARGS`` has the C signature's length (the stream excluded)."""
+    from photoverse_amd import _lib
+    assert len(A.ARGS[launcher]) == len(_lib.SIGNATURES[launcher][1]) - 1
+    assert not (set(A.ARGS[launcher]) - A.args_read(launcher)), set(A.ARGS[launcher]) - A.args_read(launcher)
+    # an argument added to the ABI that nobody models shows up as unread
+    monkeypatch.setitem(A.ARGS, launcher, A.ARGS[launcher] + ("an_argument_nobody_models",))
+    assert set(A.ARGS[launcher]) - A.args_read(launcher) == {"an_argument_nobody_models"}

@@ -4,8 +4,13 @@ launch's own parameter block, ``oracle.abi_ref``'s derived element and aggregate
 every byte of the output storages outside the described extents, a bit-identical second run - on guarded tensors: outputs sit inside a patterned arena a
 stray tile cannot leave, inputs inside NaN, so a read outside an input's extent that reaches a result fails the finite check.
 
-Wall time of this file alone on one MI355X: 7.3 s for its 127 tests (5.3 s of it in the audits, 177 launches); the rest of the GPU suite on the same box,
-same visit: 181.0 s for 314 tests (EXPERIMENTS.md, "Edge audit")."""
+Since the newer loop features and the pre-loop conditioning joined the catalogue (the guided / stochastic / PAG steps, FreeU, the resize, the fp32 pointwise
+launchers, ``pv_rows_mean``, the casts, patchify, the two embeds, ``pv_fusion_draw``; 51 cases, 345 launches, a group of them at the product's shapes) a case
+may also name pairs of outputs that must agree bit for bit (the launchers' documented substitutions).
+
+Wall time of this file alone on one MI355X: 7.19 s for its 178 tests (5.2 s of it in the audits, 522 launches; every one of the 51 newer cases below 0.1 s);
+the parent commit's file on the same box, same visit: 7.03 s for 127 tests (177 launches); the whole GPU suite then: 231.0 s for 573 tests (EXPERIMENTS.md,
+"Edge audit")."""
 import time
 
 import pytest
@@ -39,6 +44,8 @@ def test_edge_case(name, auditor):
             for want in c.expect:
                 assert want in tags, (want, tags)
             n = auditor.audit(name, rec)
+            for a, b in getattr(rec, "same_bits", ()):      # pairs of outputs the case promises to be the same launch: bit for bit, not within a bound
+                assert torch.equal(a, b), f"{name}: two launches that must be the same kernel on the same inputs differ in {(a != b).sum().item()} elements"
     except AssertionError:
         raise
     except Exception as e:                      # a HIP error: nothing more is started on a device that has faulted

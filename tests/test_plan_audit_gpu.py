@@ -1,7 +1,15 @@
 """Every launch of the inference plans, one at a time, against its fp64 reference (``oracle.plan_audit`` / ``oracle.abi_ref``), at the shapes
 the product gives it: pointers resolved to held tensors (use-after-free check), outputs poisoned, element-wise and aggregate bounds, the bytes
 around every output, column statistics, and a bit-identical second run.  Plus every batch position of the headline plan against the B = 1
-plan the oracle pins."""
+plan the oracle pins.
+
+Besides the default loops and the VAE: the loops the newer features build (image guidance + rescale + inpainting, the same with the stochastic sampler,
+PAG over a shared trunk with FreeU) on the tiny UNet, the pre-loop conditioning plans at full size (CLIP vision and text encoders, both adapters) and
+the recorders ``run_inference`` builds around the loop (hires pre-pass, inpaint pre- and post-pass).
+
+Wall time on one MI355X, this file alone: 52.3 s for its 11 tests - the three feature loops 0.6 s each (349 / 349 / 324 launches), the conditioning plans
+2.2 s (367 launches), the hires / inpaint recorders below 0.1 s (5 launches); the parent commit's file on the same box, same visit: 49.8 s for 6 tests
+(EXPERIMENTS.md, "Edge audit")."""
 import time
 import zlib
 
@@ -41,9 +49,11 @@ def _recorders(loop):
     return out
 
 
-def _audit_loop(aud, plan, loop, seed):
-    """Conditioning, every launch of the first denoising step in a valid serial order (prefix, heads u / c, merged, tails u / c, tail), then the
-    second step's tail (the solver's second-order update).  Returns (audited, recorded)."""
+def _audit_loop(aud, plan, loop, seed, prepare=None):
+    """Conditioning, every launch of the first denoising step in a valid serial order (prefix, heads u / c, merged, tails u / c, tail - without a
+    merged plan: the uncond, cond and image-only forwards, the perturbed one right behind its conditional forward, whose trunk it may share), then the
+    second step's tail (the solver's second-order update).  ``prepare(loop)`` fills the static buffers of a feature loop (mask, noise stream) before
+    the reset.  Returns (audited, recorded)."""
     B, S, P = loop.B, loop.S, loop.P
     cond, uncond, noise = _conditioning(B, S, P, seed)
     for (text, ip), (dt, di) in ((cond, (loop.text_c, loop.ip_c)), (uncond, (loop.text_u, loop.ip_u))):
@@ -59,6 +69,8 @@ def _audit_loop(aud, plan, loop, seed):
 
     for e in loop.all_engines:
         run("cond", e.rec_cond)
+    if prepare is not None:
+        prepare(loop)
     loop.reset(noise)
     step = []
     step += [e.rec for e in loop.engines_p]
@@ -66,7 +78,9 @@ def _audit_loop(aud, plan, loop, seed):
         (eu,), (ec,), (em,) = loop.engines_u, loop.engines_c, loop.engines_m
         step += [eu.rec_head, ec.rec_head, em.rec, eu.rec_tail, ec.rec_tail]
     else:
-        step += [e.rec for e in loop.engines_u + loop.engines_c]
+        after = loop._after_cond()
+        for e in loop.engines_u + loop.engines_c + loop.engines_i:
+            step += [e.rec] + ([after[id(e)].rec] if id(e) in after else [])
     for r in step:
         run("step1", r)
     run("tail1", loop.tail)
@@ -172,3 +186,164 @@ def test_headline_plan_every_batch_position_matches_bs1(full_hip_unet):
         errs.append(rel_l2(got[i:i + 1], ref))
     print("headline plan vs B = 1 plan after 10 steps, per batch position:", " ".join(f"{e:.2e}" for e in errs))
     assert max(errs) < 1e-3, errs
+
+
+# ------------------------------------------------------------------------------------------------------------------ feature loops on the tiny UNet
+def _no_new_launch_after_a_hip_error(fn):
+    """An AuditError is a finding (the test fails); anything else is a HIP error: nothing more is started on a device that has faulted."""
+    try:
+        return fn()
+    except AssertionError:
+        raise
+    except Exception as e:
+        pytest.exit(f"plan audit: {type(e).__name__}: {e}", returncode=3)
+
+
+@pytest.fixture(scope="module")
+def tiny_hip():
+    from oracle.unet_ref import TINY_CONFIG, UNet2DConditionModelRef, set_visual_cross_attention_adapter_ref
+    from photoverse_amd.unet import UNet2DConditionModel, set_visual_cross_attention_adapter
+    torch.manual_seed(0)
+    ref = UNet2DConditionModelRef(**TINY_CONFIG).eval()
+    set_visual_cross_attention_adapter_ref(ref, (5,))
+    hip = UNet2DConditionModel(**TINY_CONFIG)
+    set_visual_cross_attention_adapter(hip, (5,))
+    hip.load_state_dict(ref.state_dict(), strict=True)
+    return hip.to("cuda")
+
+
+def _inpaint_and_stream(loop):
+    g = torch.Generator().manual_seed(5)
+    if loop.inpaint:
+        r = torch.rand(loop.B, 1, loop.S, loop.S, generator=g)
+        mask = torch.where(r < 0.3, torch.zeros(()), torch.where(r > 0.7, torch.ones(()), r))            # zeros, ones and fractions
+        loop.set_inpaint(mask.cuda(), torch.randn(loop.latents.shape, generator=g).cuda(), torch.randn(loop.latents.shape, generator=g).cuda())
+    if loop.stochastic:
+        loop.set_noise_stream(0x8000_0001_9000_0007, sample_offset=0xFFFFFFFF, stream=3)
+
+
+GUIDED = dict(image_guidance_scale=3.0, guidance_rescale=0.7, inpaint=True)
+FEATURE_LOOPS = {
+    "h-guided": (dict(GUIDED), "pv_cfg_dpm_step_guided", ()),
+    "i-stochastic": (dict(GUIDED, stochastic=True), "pv_cfg_dpm_step_stochastic", ()),
+    "j-pag-freeu": (dict(pag_scale=2.0, pag_layers=("mid_block", "up_blocks.1.attentions.0"), freeu=(1.5, 1.6, 0.9, 0.2), share_trunk=True), "pv_cfg_dpm_step_pag",
+                    ("freeu_rows_kernel",)),
+}
+
+
+@pytest.mark.parametrize("plan", list(FEATURE_LOOPS))
+def test_plan_audit_feature_loops(plan, tiny_hip, auditor):
+    """Every recorder of the loops the newer features build on the tiny UNet (B = 2, 16 x 16): three forwards with rescale and inpainting, the same
+    as the stochastic sampler, and PAG on the mid block and an up-block layer over a shared trunk with FreeU."""
+    from photoverse_amd.pipeline import DenoiseLoop
+    kw, step_launcher, tags = FEATURE_LOOPS[plan]
+    t0 = time.time()
+    loop = DenoiseLoop(tiny_hip, 2, 16, 1, 4, 7.5, **kw)
+    assert (len(loop.engines_i) == 1) == ("image_guidance_scale" in kw) and (len(loop.engines_p_attn) == 1) == ("pag_scale" in kw)
+    n_aud, n_rec = _no_new_launch_after_a_hip_error(lambda: _audit_loop(auditor, plan, loop, seed=zlib.crc32(plan.encode()) % 10000, prepare=_inpaint_and_stream))
+    print(f"\n{plan}: audited {n_aud} of {n_rec} recorded launches in {time.time() - t0:.1f} s")
+    assert n_aud == n_rec and n_rec > 0
+    rows = [k for k in auditor.rows if k[0] == plan]
+    assert any(k[1] == step_launcher for k in rows), (plan, step_launcher)
+    for tag in tags:
+        assert any(k[2] == tag for k in rows), (plan, tag)
+    del loop
+    torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------------------------------------------------------ conditioning plans, full size
+def _spy_recorders(monkeypatch, *modules):
+    """Recorders a function builds for itself (the adapters' forward, ``hires_start``, ``scheduler.add_noise``) are caught as they are made."""
+    from photoverse_amd import ops
+    made = []
+
+    class Spy(ops.Recorder):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            made.append(self)
+    for m in modules:
+        monkeypatch.setattr(m, "Recorder", Spy)
+    return made
+
+
+def test_plan_audit_conditioning(full_weights, auditor, monkeypatch):
+    """The pre-loop plans at full size, B = 1: the CLIP vision encoder (24 layers, 257 tokens), the CLIP text encoder without and with the product's one
+    concept token, both adapters on the vision plan's own hidden states."""
+    from photoverse_amd import adapters
+    from photoverse_amd.adapters import PhotoVerseAdapter
+    from photoverse_amd.clip import CLIPTextModel, CLIPVisionModel
+    dev = torch.device("cuda")
+    case = fs.pipeline_case()
+    t0 = time.time()
+    with fs.no_init():
+        vis, txt = CLIPVisionModel(), CLIPTextModel()
+        ads = {"image_adapter": PhotoVerseAdapter(1024, 768, 5), "text_adapter": PhotoVerseAdapter(1024, 768, 5)}
+    vis.load_state_dict(full_weights("vision"))
+    txt.load_state_dict(full_weights("text"))
+    vis.to(dev), txt.to(dev)
+    counts = {}
+
+    def audit(plan, rec):
+        counts[plan] = (_no_new_launch_after_a_hip_error(lambda: auditor.audit(plan, rec)), len(rec.calls))
+
+    vp = vis._plan(1, dev)
+    vp.pixels.copy_(case["example"]["pixel_values_clip"])
+    audit("k-clip-vision", vp.rec)
+    embs = [vp.hs[-1].view(1, vp.ntok, vp.dim)] + [vp.hs[i].view(1, vp.ntok, vp.dim) for i in case["layers"]]
+    made = _spy_recorders(monkeypatch, adapters)
+    concept = None
+    for name, ad in ads.items():
+        ad.load_state_dict(full_weights(name))
+        ad.to(dev)
+        with torch.no_grad():
+            out = ad(embs, token_index=case["token_index"])
+        concept = out if name == "text_adapter" else concept
+        audit(f"l-{name.replace('_', '-')}", made[-1])
+    for E in (0, 1):
+        tp = txt._plan(1, 77, E, dev)
+        tp.ids.copy_(case["example"]["text_input_ids"] if E else case["uncond_ids"])
+        if E:
+            assert concept.shape == (1, E, 768)
+            tp.concept.copy_(concept.reshape(E, -1))
+            tp.pidx.copy_(case["example"]["concept_placeholder_idx"].reshape(-1))
+        audit(f"m-clip-text-e{E}", tp.rec)
+    print(f"\nconditioning: " + ", ".join(f"{k} {a} of {n}" for k, (a, n) in counts.items()) + f" launches audited in {time.time() - t0:.1f} s")
+    assert all(a == n and n > 0 for a, n in counts.values()), counts
+    rows = list(auditor.rows)
+    assert any(k[0].startswith("m-clip-text") and k[1] == "pv_attention" and "causal" in k[4] and "d=64" in k[4] for k in rows)
+    for launcher in ("pv_clip_text_embed", "pv_patchify", "pv_clip_vision_embed", "pv_rows_mean"):
+        assert any(k[1] == launcher for k in rows), launcher
+    assert any(k[1] == "pv_clip_text_embed" and "n_concept" in k[4] for k in rows) and any(k[1] == "pv_clip_text_embed" and not k[4] for k in rows)
+    assert any(k[1] == "pv_rows_mean" and "accumulate" in k[4] for k in rows)
+
+
+def test_plan_audit_hires_and_inpaint_recorders(auditor, monkeypatch):
+    """The recorders ``infer.run_inference`` builds around the loop, at 64 -> 96, B = 1: the hires pre-pass (``hires_start``), the inpaint pre-pass
+    (``scheduler.add_noise``) and the post-pass (1 / scaling_factor, paste-back + clamp on the 768-pixel image, the plain clamp)."""
+    from photoverse_amd import ops
+    from photoverse_amd.infer import hires_start
+    from photoverse_amd.scheduler import DPMSolverMultistepScheduler
+    g = torch.Generator().manual_seed(43)
+    t0 = time.time()
+    made = _spy_recorders(monkeypatch, ops)
+    sch = DPMSolverMultistepScheduler()
+    x_start, start = hires_start(torch.randn(1, 4, 64, 64, generator=g).cuda(), torch.randn(1, 4, 96, 96, generator=g).cuda(), sch, 50, 0.5)
+    assert start == 25 and tuple(x_start.shape) == (1, 4, 96, 96) and len(made) == 1
+    sch.set_timesteps(50)
+    sch.add_noise(torch.randn(1, 4, 96, 96, generator=g).cuda(), torch.randn(1, 4, 96, 96, generator=g).cuda(), sch.timesteps[10:11])
+    assert len(made) == 2
+    post = ops.Recorder(torch.device("cuda"))                       # infer.py's post-pass, launch for launch
+    post.affine_rows(torch.randn(1, 4, 96, 96, generator=g).cuda(), torch.full((1,), 1.0 / 0.18215).cuda())
+    images = (torch.randn(1, 3, 768, 768, generator=g) * 0.8).cuda()
+    mask = (torch.rand(1, 1, 768, 768, generator=g) > 0.5).float().cuda()
+    post.composite_clamp(images, (torch.rand(1, 3, 768, 768, generator=g) * 2 - 1).cuda(), mask, -1.0, 1.0, out=images)
+    post.clamp_((torch.randn(1, 3, 768, 768, generator=g) * 0.8).cuda(), -1.0, 1.0)
+    counts = {}
+    for plan, rec in (("n-hires-pre", made[0]), ("o-inpaint-pre", made[1]), ("p-post", post)):
+        counts[plan] = (_no_new_launch_after_a_hip_error(lambda: auditor.audit(plan, rec)), len(rec.calls))
+    print(f"\nhires / inpaint recorders: " + ", ".join(f"{k} {a} of {n}" for k, (a, n) in counts.items()) + f" launches audited in {time.time() - t0:.1f} s")
+    assert all(a == n and n > 0 for a, n in counts.values()), counts
+    rows = list(auditor.rows)
+    for plan, launcher in (("n-hires-pre", "pv_resize_bilinear_affine_f32"), ("o-inpaint-pre", "pv_affine_rows_f32"), ("p-post", "pv_composite_clamp_f32"),
+                           ("p-post", "pv_clamp_f32"), ("p-post", "pv_affine_rows_f32")):
+        assert any(k[0] == plan and k[1] == launcher for k in rows), (plan, launcher)
