@@ -215,7 +215,11 @@ int pv_act_forward(const void* x, int32_t ldx, void* y, int32_t ldy, int32_t row
 /* Dropout on the input of a LoRA branch (peft LoRA layer: result += B(A(dropout(x))) * scaling; train.py:265-270).  Counter-based
  * (Philox4x32-10): the keep mask is a function of (rng key, site, rng[2] = iteration, copy, element), recomputed by the backward.
  * forward: out[r][k*cols + c] = x[r][c] * keep_k / (1-p), k < copies (several independently masked copies side by side);
- * backward: out[r][c] = sum_k x[r][k*cols + c] * keep_k / (1-p) (+ add).  rng: the {key lo, key hi, counter} block of pv_fusion_draw. */
+ * backward: out[r][c] = sum_k x[r][k*cols + c] * keep_k / (1-p) (+ add).  rng: the {key lo, key hi, counter} block of pv_fusion_draw.
+ * The mask: the 8-column chunk q = r * (cols / 8) + c / 8 of copy k draws ONE Philox block, key (rng[0], rng[1]), counter (q, site, rng[2], k); its
+ * element j = c % 8 takes the 16-bit lane (word[j / 2] >> (16 * (j % 2))) & 0xFFFF and is kept when lane >= uint32(p * 65536) (p = 0 keeps
+ * everything).  1 / (1 - p) is formed in fp32; the backward adds `add`, then the copies in k order, in fp32; one fp16 rounding at the store.
+ * cols % 8 == 0, 1 <= copies <= 4, 0 <= p < 1. */
 int pv_dropout_f16(const void* x, int32_t ldx, void* out, int32_t ldo, const void* add, int32_t ldadd, int32_t rows, int32_t cols, int32_t copies,
                    float p, const int32_t* rng, int32_t site, int32_t backward, void* stream);
 /* ---- the ArcFace identity loss (models/loss.py, models/arcface_resnet.py; train.py:521-535) and the VAE-decoder backward under it ---- */
@@ -228,11 +232,17 @@ int pv_prelu_f16(const void* x, int32_t ldx, const void* dy, int32_t lddy, const
 /* nn.MaxPool2d(2, 2) over NHWC fp16 (B,h,w,c): dy == NULL: out (B,h/2,w/2,c); else out (B,h,w,c) = dy routed to each window's first maximum */
 int pv_maxpool2x2(const void* x, const void* dy, void* out, int32_t batch, int32_t h, int32_t w, int32_t c, void* stream);
 /* FaceLoss.preprocess (loss.py:26-62): y (B,1,size,size) = bilinear(align_corners=False) of gray(x) * mul + add; x fp32 (B,3,h,w) with the given
- * image stride (elements).  _backward: dx (B,3,h,w) contiguous from dy (B,1,size,size) with its image stride; deterministic gather */
+ * image stride (elements).  _backward: dx (B,3,h,w) contiguous from dy (B,1,size,size) with its image stride; deterministic gather.
+ * gray = 0.2989 r + 0.5870 g + 0.1140 b.  Taps of one axis (in -> size), evaluated in fp32 as written: src = max((o + 0.5) * (in / size) - 0.5, 0),
+ * i0 = min(floor(src), in - 1), i1 = min(i0 + 1, in - 1), weights (1 - t, t) with t = src - i0; y = (1 - ty) * row(y0) + ty * row(y1), each row
+ * (1 - tx) * gray[x0] + tx * gray[x1].  The backward gives input pixel (iy, ix) the sum over the outputs whose taps include it of
+ * wy(oy, iy) * wx(ox, ix) * dy[oy][ox], outputs in row-major order, times mul, times the channel's gray weight. */
 int pv_gray_resize(const float* x, int64_t x_image_stride, float* y, int32_t batch, int32_t h, int32_t w, int32_t size, float mul, float add, void* stream);
 int pv_gray_resize_backward(const float* dy, int64_t dy_image_stride, float* dx, int32_t batch, int32_t h, int32_t w, int32_t size, float mul, void* stream);
 /* nn.CosineEmbeddingLoss (margin 0) per sample: target > 0: 1 - cos(e1, e2), else max(0, cos); e1 / e2 fp16 [batch][dim];
- * de2 (optional, fp16) = gscale / batch * d(loss_b)/d(e2_b) - the gradient of the batch MEAN times gscale */
+ * de2 (optional, fp16) = gscale / batch * d(loss_b)/d(e2_b) - the gradient of the batch MEAN times gscale.
+ * cos = ab / sqrt((aa + 1e-8) * (cc + 1e-8)) with ab = e1.e2, aa = e1.e1, cc = e2.e2 (fp32: 64 lanes of ceil(dim / 64) terms each, then a tree);
+ * d(cos)/d(e2) = e1 / sqrt(..) - cos * e2 / (cc + 1e-8); a cosine <= 0 with target <= 0 has loss 0 and gradient 0. */
 int pv_cosine_embedding_loss(const void* e1, const void* e2, int32_t batch, int32_t dim, float target, float gscale, float* per_sample, void* de2,
                              void* stream);
 /* in-place backward of pv_softmax_rows: dp <- scale * p * (dp - sum_j p_j dp_j) per row */
@@ -398,7 +408,12 @@ int pv_cross_attention_backward(const pv_xattn_bwd_params* p, void* stream);
 /* out[c][r] = x[r][c] (fp16), rows zero-padded to rows_pad: operand layout of dW = dY^T . X on pv_gemm_conv */
 int pv_transpose_f16(const void* x, int32_t ldx, int32_t rows, int32_t cols, void* out, int32_t ldo, int32_t rows_pad, void* stream);
 /* LayerNorm (+ LeakyReLU) backward (adapters.py:15-19): dx fp16; dgb_partial (optional) fp32 [ceil(rows / (4 * rows_per_wave))][2][cols] =
- * per-row-block (dgamma, dbeta) terms, to be summed with pv_reduce_blocks */
+ * per-row-block (dgamma, dbeta) terms, to be summed with pv_reduce_blocks.  act: PV_ACT_NONE or PV_ACT_LEAKY_RELU.
+ *   g = dy * dy_scale * act'(gamma * xhat + beta), dxhat = g * gamma, dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat)) (+ add);
+ *   block b of dgb_partial = (sum g * xhat, sum g) over its rows (each wave its rows_per_wave rows in order, then the four waves in order).
+ * Without dgb_partial, with cols % 8 == 0 and every row stride a multiple of 8, a vector form runs LPR lanes per row (4 * 64 / LPR rows per
+ * workgroup), chosen by cols / 8: <= 40: 8, <= 96: 16, <= 160: 32, else 64 (six instantiations: <= 40, 80, 96, 128, 160 chunks and above);
+ * otherwise one wave per row.  cols <= 2048. */
 typedef struct pv_layernorm_bwd_params {
     const void* x; int32_t ldx;
     const void* dy; int32_t lddy;
@@ -415,9 +430,11 @@ typedef struct pv_layernorm_bwd_params {
                                        /* consumers - the residual stream: one launch instead of the gradient + an add pass) (ABI 14) */
 } pv_layernorm_bwd_params;
 int pv_layernorm_backward(const pv_layernorm_bwd_params* p, void* stream);
-/* out[i] = scale * sum_b x[b][i], b in order (deterministic) */
+/* out[i] = scale * sum_b x[b][i] (x: fp32 [nblk][inner]), in a fixed order (deterministic): eight groups, group g adds the blocks g, g + 8, g + 16, ...
+ * - while four of them 8 apart remain, into four accumulators (a0..a3, each taking every 32nd block), the up to three left over into a0 - and
+ * closes with (a0 + a1) + (a2 + a3); the eight group sums are then added in g order and multiplied by scale. */
 int pv_reduce_blocks(const float* x, int32_t nblk, int64_t inner, float scale, float* out, void* stream);
-/* out[0] = scale * sum(a^2), deterministic (gradient norms of clip_grad_norm_) */
+/* out[0] = scale * sum(a^2), deterministic (gradient norms of clip_grad_norm_): the reduction order of pv_reduce_mean (partial: n_partial floats) */
 int pv_reduce_sumsq(const float* a, int64_t n, float scale, float* partial, int32_t n_partial, float* out, void* stream);
 /* Multi-tensor forms of the three optimizer launches: ONE launch each over every parameter tensor.  entries: int64 [T][6] =
  * {param, grad, exp_avg, exp_avg_sq, gscale pointer (or 0), n}; workgroup b handles elements [blk_chunk[b] * chunk, + chunk) of tensor
@@ -442,7 +459,9 @@ int pv_adamw_multi(const int64_t* entries, const int32_t* blk_tensor, const int3
  * over ceil(rows/32) x ceil(cols/32)) of entry blk_entry[b].  A destination may be a block of a larger zero-padded matrix (block-diagonal LoRA
  * factors, stacked k / v projections). */
 int pv_pack_weights(const int64_t* entries, const int32_t* blk_entry, const int32_t* blk_tile, int32_t n_blocks, void* stream);
-/* out[c] = sum_r x[r][c] over fp16 rows (bias gradients); partial: nblk*cols floats */
+/* out[c] = sum_r x[r][c] over fp16 rows (bias gradients); partial: nblk*cols floats of workspace.  Block b adds the rows
+ * [b * rpb, min(rows, (b + 1) * rpb)), rpb = ceil(rows / nblk), in row order in fp32 (a block past the last row holds 0); the nblk block sums are
+ * then added in pv_reduce_blocks' order. */
 int pv_colsum_f16(const void* x, int32_t ldx, int32_t rows, int32_t cols, float* partial, int32_t nblk, float* out, void* stream);
 
 /* GEGLU gate (diffusers GEGLU, exact-erf GELU): out[m][j] = x[m][j] * gelu(x[m][n+j]) */
@@ -595,7 +614,10 @@ int pv_freeu_rows(const void* x, int32_t ldx, int32_t cx, void* x_out, int32_t l
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);
 /* deterministic mean reductions of the training losses (train.py:509-516): mode 0 mean(a), 1 mean|a| (concept_text_loss),
- * 2 mean((a-b)^2) (F.mse_loss); a / b fp32 or fp16 (is_f16); partial: workspace of n_partial floats; out[0] = result */
+ * 2 mean((a-b)^2) (F.mse_loss); a / b fp32 or fp16 (is_f16); partial: workspace of n_partial floats; out[0] = result.
+ * Order (fp32): n_partial workgroups of 256 threads; thread t of workgroup w adds the elements 256 w + t, + 256 n_partial, ... in order; a
+ * 6-level butterfly per 64-lane wave, the four waves as (w0 + w1) + (w2 + w3) -> partial[w]; the partials are added in w order and multiplied by
+ * the fp32 1 / n (pv_reduce_sumsq: by scale). */
 int pv_reduce_mean(const void* a, const void* b, int32_t mode, int32_t is_f16, int64_t n, float* partial, int32_t n_partial,
                    float* out, void* stream);
 

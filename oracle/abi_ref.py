@@ -26,6 +26,13 @@ convolution is nine shifted matmuls.  Error bounds (every constant derived here,
   error is its longest addition chain times U32 (``step_chain``, ``freeu_chain``: the chains of the kernels' documented reduction orders), not its
   length.  One term is measured, not derived: ``TOL_NOISE``, the error the device's ``logf`` / ``sincospif`` leave on a generated normal.
 
+* the training tape's single launches (``TRAINING``): the pointwise fp16 launchers carry the store rounding and a few U32 of their fp32 expression
+  (``__expf`` derived from the ISA's one-ulp exp2 / rcp, ``GELU_APPROX`` through the GELU forms and their derivatives); exact-select launchers compare
+  bit for bit; reductions take the longest chain of their documented order (``blocks_chain``, ``mean_chain``, ``ln_bwd_chain``); ``pv_wgrad_tn`` takes
+  ``mfma_c(rows_per_split)`` per slab.  Branch points - the LeakyReLU of ``pv_layernorm_backward``, the max(0, cos) of the cosine loss - widen the bound of
+  the elements within their own fp32 error of the branch by the branch difference; the integer tap boundaries of the gray resizes need no widening, the
+  bilinear weights being continuous across them (``gray_taps``).
+
 Every function of the C ABI is in exactly one of ``REF`` (audited) and ``NOT_AUDITED`` (outside the audit, with the reason).  A buffer whose extent
 depends on the contents of another one (the coefficient row by the step counter, the token table by the ids) is listed in ``DEPENDENT``.
 
@@ -57,7 +64,9 @@ KAPPA = 6.0
 
 #: aggregate rel-L2 tolerances the kernel tests assert for each launcher (tests/test_hip_kernels.py): no audit bound is looser
 CAP = {"gemm16": 1e-3, "gemm32": 2e-5, "attention": 2e-3, "xattn": 2e-3, "lnq": 2e-3, "fused": 1e-3, "fused_attn": 3e-3, "row_gemm": 1e-3,
-       "layernorm": 1e-3, "groupnorm": 1e-3, "conv_out": 1e-5}
+       "layernorm": 1e-3, "groupnorm": 1e-3, "conv_out": 1e-5,
+       # the training tape's launchers (test_elementwise_backward_pieces, test_arcface_loss_pieces, test_layernorm_backward_kernels; wgrad: ``wgrad_cap``)
+       "pointwise16": 1e-3, "pointwise_bwd": 2e-3, "gray": 1e-5, "ln_bwd_dx": 1.5e-3, "ln_bwd_dgb": 1e-4}
 
 
 def mfma_c(k: int) -> float:
@@ -1293,6 +1302,592 @@ def ref_text_embed(p, v):
     return {"out": expect((val + pos).reshape(B * S, dim), (U32 * (val.abs() + pos.abs())).reshape(B * S, dim), F16)}
 
 
+# ===================================================================================================================== the training tape: pointwise
+# Single launches of the training tape (the backward passes of the stock blocks, the ArcFace identity loss, the reductions of the losses and of the
+# optimizer): the same rules - semantics from the header alone, fp64 on the exact fp16 / fp32 inputs, every constant derived.
+#
+# The fp32 expressions of the pointwise fp16 launchers are a handful of operations; their error sits three orders below the fp16 store (U32 / U16 =
+# 2^-13).  What is used of the device, from the CDNA ISA's documented accuracy: v_exp_f32, v_rcp_f32 and v_rsq_f32 are within one ulp (2 U32); a division
+# is allowed two ulps (4 U32).  ``__expf(t)`` is exp2 of the rounded product t log2 e: the product's rounding moves the exponent by U32 |t| log2 e, the
+# exponential by ln 2 times that, relative: |t| U32; with exp2's own ulp: (|t| + 2) U32 - derived, so no measured term enters these bounds.
+# sigmoid(t) = 1 / (1 + e), e = exp(-t): the relative error of e reaches s scaled by e / (1 + e) = 1 - s; the sum and the division add 5 U32.
+ACT_NAMES = {0: "none", 1: "silu", 2: "quick-gelu", 3: "leaky-relu", 4: "gelu"}
+
+
+def _sigmoid_err(t, s):
+    """Relative error of the fp32 sigmoid(t) as the kernels form it (1 / (1 + __expf(-t))), in units of U32."""
+    return (t.abs() + 3) * (1 - s) + 5
+
+
+def _pdf(x):
+    return torch.exp(-0.5 * x * x) / math.sqrt(2 * math.pi)
+
+
+def _cdf(x):
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def _act_grad(x, act):
+    """(act'(x), its absolute fp32 error bound) for the activation codes of the header."""
+    if act == 0:
+        return torch.ones_like(x), torch.zeros_like(x)
+    if act in (1, 2):
+        a = 1.0 if act == 1 else 1.702
+        s = torch.sigmoid(a * x)
+        g = s * (1 + a * x * (1 - s))
+        # s carries R U32 relative; 1 - s then s R U32 absolute; the products and the sum round four times
+        R = _sigmoid_err(a * x, s)
+        return g, U32 * (R * (g.abs() + s * s * (a * x).abs()) + 4 * s * (1 + (a * x).abs() * (1 - s)))
+    if act == 3:
+        g = torch.where(x > 0, torch.ones_like(x), torch.full_like(x, 0.01))
+        return g, U32 * g                                   # 0.01f is the fp32 nearest to 0.01
+    if act == 4:
+        pdf = _pdf(x)
+        g = _cdf(x) + x * pdf
+        # Phi through an erf approximation: GELU_APPROX |x| on gelu is GELU_APPROX on its derivative; phi through __expf(-x^2 / 2)
+        return g, GELU_APPROX + U32 * ((0.5 * x * x + 4) * (x * pdf).abs() + 4 * g.abs())
+    raise ValueError(f"unknown activation {act}")
+
+
+def _act_err(x, y, act):
+    """Absolute fp32 error bound of y = act(x) before the store."""
+    if act == 0:
+        return torch.zeros_like(x)
+    if act in (1, 2):
+        a = 1.0 if act == 1 else 1.702
+        return U32 * (_sigmoid_err(a * x, torch.sigmoid(a * x)) + 2) * y.abs()
+    if act == 3:
+        return 2 * U32 * y.abs()
+    return (GELU_APPROX + 8 * U32) * x.abs()
+
+
+def layout_act_forward(p):
+    return {"x": Buf(F16, p.rows, p.cols, p.ldx), "y": Buf(F16, p.rows, p.cols, p.ldy, "out")}
+
+
+def ref_act_forward(p, v):
+    x = f64(v["x"])
+    y = _act(x, p.act)
+    return {"y": expect(y, _act_err(x, y, p.act), F16, cap=CAP["pointwise16"])}
+
+
+def layout_act_backward(p):
+    return {"x": Buf(F16, p.rows, p.cols, p.ldx), "dy": Buf(F16, p.rows, p.cols, p.lddy), "dx": Buf(F16, p.rows, p.cols, p.lddx, "out")}
+
+
+def ref_act_backward(p, v):
+    """dx = dy act'(x): the derivative's error times |dy|, and the product's rounding."""
+    x, dy = f64(v["x"]), f64(v["dy"])
+    g, eg = _act_grad(x, p.act)
+    return {"dx": expect(dy * g, dy.abs() * eg + U32 * (dy * g).abs(), F16, cap=CAP["pointwise_bwd"])}
+
+
+def layout_geglu(p):
+    return {"x": Buf(F16, p.rows, 2 * p.n, p.ldx), "out": Buf(F16, p.rows, p.n, p.ldo, "out")}
+
+
+def ref_geglu(p, v):
+    x = f64(v["x"])
+    a, g = x[:, :p.n], x[:, p.n:]
+    y = a * _gelu(g)
+    return {"out": expect(y, a.abs() * (GELU_APPROX + 8 * U32) * g.abs() + U32 * y.abs(), F16, cap=CAP["pointwise16"])}
+
+
+def layout_geglu_backward(p):
+    return {"h": Buf(F16, p.rows, 2 * p.n, p.ldh), "dy": Buf(F16, p.rows, p.n, p.lddy), "dh": Buf(F16, p.rows, 2 * p.n, p.lddh, "out")}
+
+
+def ref_geglu_backward(p, v):
+    """y = a gelu(g), h = [a | g]: dh = [dy gelu(g) | dy a gelu'(g)]."""
+    h, dy = f64(v["h"]), f64(v["dy"])
+    a, g = h[:, :p.n], h[:, p.n:]
+    gp, egp = _act_grad(g, 4)
+    da, dg = dy * _gelu(g), dy * a * gp
+    eda = dy.abs() * (GELU_APPROX + 8 * U32) * g.abs() + U32 * da.abs()
+    edg = (dy * a).abs() * egp + 2 * U32 * dg.abs()
+    return {"dh": expect(torch.cat([da, dg], 1), torch.cat([eda, edg], 1), F16, cap=CAP["pointwise_bwd"])}
+
+
+def layout_col_affine(p):
+    L = {"x": Buf(F16, p.rows, p.cols, p.ldx), "scale": Buf(F32, 1, p.cols, 0), "y": Buf(F16, p.rows, p.cols, p.ldy, "out")}
+    if _ptr(p, "shift"):
+        L["shift"] = Buf(F32, 1, p.cols, 0)
+    return L
+
+
+def ref_col_affine(p, v):
+    t = f64(v["x"]) * f64(v["scale"])
+    sh = f64(v["shift"]) if "shift" in v else torch.zeros_like(t[:1])
+    return {"y": expect(t + sh, 2 * U32 * (t.abs() + sh.abs()), F16, cap=CAP["pointwise16"])}
+
+
+def layout_prelu(p):
+    L = {"x": Buf(F16, p.rows, p.cols, p.ldx), "slope": Buf(F32, 1, 1, 0), "out": Buf(F16, p.rows, p.cols, p.ldo, "out")}
+    if _ptr(p, "dy"):
+        L["dy"] = Buf(F16, p.rows, p.cols, p.lddy)
+    return L
+
+
+def ref_prelu(p, v):
+    """dy NULL: x > 0 ? x : a x; else dy (x > 0 ? 1 : a) - x = 0 takes the slope branch.  One fp32 product."""
+    x, a = f64(v["x"]), f64(v["slope"]).reshape(())
+    k = torch.where(x > 0, torch.ones_like(x), a * torch.ones_like(x))
+    y = (f64(v["dy"]) if "dy" in v else x) * k
+    return {"out": expect(y, U32 * y.abs(), F16, cap=CAP["pointwise16"])}
+
+
+def layout_add_rows(p):
+    return {"a": Buf(F16, p.rows, p.cols, p.lda), "b": Buf(F16, p.rows, p.cols, p.ldb), "out": Buf(F16, p.rows, p.cols, p.ldo, "out")}
+
+
+def ref_add_rows(p, v):
+    """fp16(float(a) + float(b)) is the correctly rounded exact sum.  The fp32 sum is inexact only when the exponents differ by 14 or more; then
+    |b| < 2^(e_a - 13), an eighth of a's fp16 ulp (a quarter of the ulp below a power of two): the fp32 result stays strictly inside the interval that
+    rounds to a, as the exact sum does.  So the compare is exact, against ``round_f16`` of the fp64 sum (exact: 40 bits at most)."""
+    r = round_f16(f64(v["a"]) + f64(v["b"]))
+    return {"out": Expect(r, torch.zeros_like(r), 0.0, None)}
+
+
+def dropout_keep(words, rows, cols, copies, p32, site):
+    """keep[k][r][c] of pv_dropout_f16 (header): chunk q = r (cols / 8) + c / 8; Philox4x32-10 block at key (rng[0], rng[1]), counter
+    (q, site, rng[2], k); element j = c % 8 takes the 16-bit lane (word[j / 2] >> 16 (j % 2)) & 0xFFFF; keep = lane >= uint32(p * 65536)."""
+    import numpy as np
+    from .philox import philox4x32_10
+    k0, k1, it = (int(w) & 0xFFFFFFFF for w in words[:3])
+    thr = int(float(p32) * 65536.0)
+    q = np.arange(rows * (cols // 8), dtype=np.uint64)
+    keep = np.empty((copies, rows, cols), dtype=bool)
+    for k in range(copies):
+        w = philox4x32_10((k0, k1), (q, int(site) & 0xFFFFFFFF, it, k))
+        lanes = np.stack([(w[j >> 1] >> np.uint32(16 * (j & 1))) & np.uint32(0xFFFF) for j in range(8)], 1)      # [chunks, 8]
+        keep[k] = (lanes >= thr).reshape(rows, cols)
+    return torch.from_numpy(keep)
+
+
+def layout_dropout(p):
+    wide = p.copies * p.cols
+    L = {"x": Buf(F16, p.rows, wide if p.backward else p.cols, p.ldx), "out": Buf(F16, p.rows, p.cols if p.backward else wide, p.ldo, "out"),
+         "rng": Buf(I32, 1, 3, 0)}
+    if p.backward and _ptr(p, "add"):
+        L["add"] = Buf(F16, p.rows, p.cols, p.ldadd)
+    return L
+
+
+def ref_dropout(p, v):
+    """inv = 1 / (1 - p) in fp32 (the difference, the reciprocal: 3 U32 with the product; p = 0: exactly 1); the backward adds ``add`` and the copies in
+    order: a chain of copies + 1."""
+    p32 = _f32(p.p)
+    keep = dropout_keep(v["rng"].reshape(-1).cpu().tolist(), p.rows, p.cols, p.copies, p32, p.site).to(v["x"].device).double()
+    inv = 1.0 / (1.0 - p32)
+    x = f64(v["x"])
+    if not p.backward:
+        y = torch.cat([x * keep[k] * inv for k in range(p.copies)], 1)
+        return {"out": expect(y, 3 * U32 * y.abs(), F16)}
+    terms = [x[:, k * p.cols:(k + 1) * p.cols] * keep[k] * inv for k in range(p.copies)]
+    if "add" in v:
+        terms.append(f64(v["add"]))
+    mag = sum(t.abs() for t in terms)
+    return {"out": expect(sum(terms), (3 + p.copies + 1) * U32 * mag, F16)}
+
+
+def layout_softmax_rows_backward(p):
+    return {"p": Buf(F16, p.rows, p.cols, p.ldp), "dp": Buf(F16, p.rows, p.cols, p.lddp, "inout")}
+
+
+def ref_softmax_rows_backward(p, v):
+    """dp <- scale p (dp - Sum_j p_j dp_j).  The dot product: 256 threads of 8 ceil(cols / 2048) terms each, a 6-level tree per wave, two levels over
+    the waves; then the difference and two products."""
+    pm, dp = f64(v["p"]), f64(v["dp"])
+    sc = _f32(p.scale)
+    dot = (pm * dp).sum(1, keepdim=True)
+    chain = 8 * ((p.cols // 8 + 255) // 256) + 6 + 2 + 1
+    edot = chain * U32 * (pm * dp).abs().sum(1, keepdim=True)
+    ref = sc * pm * (dp - dot)
+    return {"dp": expect(ref, (sc * pm).abs() * (edot + 3 * U32 * (dp.abs() + dot.abs())), F16, cap=CAP["pointwise_bwd"])}
+
+
+# ===================================================================================================================== the training tape: layout, exact
+def layout_transpose(p):
+    return {"x": Buf(F16, p.rows, p.cols, p.ldx), "out": Buf(F16, p.cols, p.rows_pad, p.ldo, "out")}
+
+
+def ref_transpose(p, v):
+    r = torch.zeros(p.cols, p.rows_pad, dtype=torch.float64, device=v["x"].device)
+    r[:, :p.rows] = f64(v["x"]).T
+    return {"out": Expect(r, torch.zeros_like(r), 0.0, None)}
+
+
+def layout_dilate(p):
+    return {"x": Buf(F16, p.batch * p.h * p.w, p.c, p.ldx), "z": Buf(F16, p.batch * 4 * p.h * p.w, p.c, p.c, "out")}
+
+
+def ref_dilate(p, v):
+    z = torch.zeros(p.batch, 2 * p.h, 2 * p.w, p.c, dtype=torch.float64, device=v["x"].device)
+    z[:, ::2, ::2] = f64(v["x"]).reshape(p.batch, p.h, p.w, p.c)
+    z = z.reshape(-1, p.c)
+    return {"z": Expect(z, torch.zeros_like(z), 0.0, None)}
+
+
+def layout_pool2x(p):
+    L = {"g": Buf(F16, p.batch * 4 * p.h * p.w, p.c, p.c), "out": Buf(F16, p.batch * p.h * p.w, p.c, p.c, "out")}
+    if _ptr(p, "add"):
+        L["add"] = Buf(F16, p.batch * p.h * p.w, p.c, p.ldadd)
+    return L
+
+
+def ref_pool2x(p, v):
+    """add, then the four taps in row-major order: an fp32 chain of four."""
+    g = f64(v["g"]).reshape(p.batch, p.h, 2, p.w, 2, p.c)
+    s, mag = g.sum((2, 4)).reshape(-1, p.c), g.abs().sum((2, 4)).reshape(-1, p.c)
+    if "add" in v:
+        s, mag = s + f64(v["add"]), mag + f64(v["add"]).abs()
+    return {"out": expect(s, 4 * U32 * mag, F16, cap=CAP["pointwise16"])}
+
+
+def layout_maxpool(p):
+    full, half = p.batch * p.h * p.w, p.batch * (p.h // 2) * (p.w // 2)
+    L = {"x": Buf(F16, full, p.c, p.c), "out": Buf(F16, full if _ptr(p, "dy") else half, p.c, p.c, "out")}
+    if _ptr(p, "dy"):
+        L["dy"] = Buf(F16, half, p.c, p.c)
+    return L
+
+
+def ref_maxpool(p, v):
+    """Windows in (0,0), (0,1), (1,0), (1,1) order; the backward routes dy to the FIRST maximum of that order, zero elsewhere.  Exact."""
+    B, h, w, c = p.batch, p.h, p.w, p.c
+    win = f64(v["x"]).reshape(B, h // 2, 2, w // 2, 2, c).permute(0, 1, 3, 2, 4, 5).reshape(B, h // 2, w // 2, 4, c)
+    mx = win.max(3).values
+    if "dy" not in v:
+        r = mx.reshape(-1, c)
+        return {"out": Expect(r, torch.zeros_like(r), 0.0, None)}
+    is_max = win == mx.unsqueeze(3)
+    first = is_max & (is_max.cumsum(3) == 1)
+    r = (first * f64(v["dy"]).reshape(B, h // 2, w // 2, 1, c)).reshape(B, h // 2, w // 2, 2, 2, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, c)
+    return {"out": Expect(r, torch.zeros_like(r), 0.0, None)}
+
+
+def layout_sign(p):
+    return {"x": Buf(F32, 1, p.n, 0), "out": Buf(F32, 1, p.n, 0, "out")}
+
+
+def ref_sign(p, v):
+    r = _f32(p.coef) * torch.sign(f64(v["x"]))
+    return {"out": Expect(r, torch.zeros_like(r), 0.0, None)}
+
+
+def layout_clamp_mask(p):
+    return {"y": Buf(F32, 1, p.n, 0), "dy": Buf(F32, 1, p.n, 0), "out": Buf(F32, 1, p.n, 0, "out")}
+
+
+def ref_clamp_mask(p, v):
+    """dy where lo < y < hi (both strict), else 0.  Exact."""
+    y, dy = f64(v["y"]), f64(v["dy"])
+    r = torch.where((y > _f32(p.lo)) & (y < _f32(p.hi)), dy, torch.zeros_like(dy))
+    return {"out": Expect(r, torch.zeros_like(r), 0.0, None)}
+
+
+def layout_gather_rows(p):
+    return {"x": Buf(F16, p.batch * p.seq, p.dim, p.ldx), "idx": Buf(I32, 1, p.batch, 0), "out": Buf(F32, 1, p.batch * p.n_e * p.dim, 0, "out")}
+
+
+def ref_gather_rows(p, v):
+    """out[b][e] = scale x[b seq + idx[b] + e] where 0 <= idx[b] + e < seq, else 0 (a row of another sample is never read): one fp32 product."""
+    x = f64(v["x"]).reshape(p.batch, p.seq, p.dim)
+    row = v["idx"].reshape(p.batch, 1).long() + torch.arange(p.n_e, device=x.device)[None, :]
+    ok = (row >= 0) & (row < p.seq)
+    r = torch.gather(x, 1, row.clamp(0, p.seq - 1)[..., None].expand(p.batch, p.n_e, p.dim)) * _f32(p.scale) * ok[..., None]
+    return {"out": expect(r.reshape(1, -1), torch.zeros(1, r.numel(), dtype=torch.float64, device=x.device), F32)}
+
+
+# ===================================================================================================================== the training tape: reductions
+def blocks_chain(nblk: int) -> int:
+    """Longest fp32 addition chain of pv_reduce_blocks (header): eight groups, group g adds blocks g, g + 8, ... into four accumulators (blocks 32 apart,
+    then at most three single ones into the first), (a0 + a1) + (a2 + a3), the eight groups in order, the product with ``scale``."""
+    return (nblk + 31) // 32 + 3 + 2 + 7 + 1
+
+
+def mean_chain(n: int, n_partial: int) -> int:
+    """pv_reduce_mean / pv_reduce_sumsq (header): n_partial workgroups of 256 threads stride over the elements (ceil(n / (256 n_partial)) terms a thread), a
+    6-level tree per wave, two levels over the four waves, the partials in order, the product with the scale."""
+    return (n + 256 * n_partial - 1) // (256 * n_partial) + 6 + 2 + n_partial + 1
+
+
+def layout_reduce_blocks(p):
+    return {"x": Buf(F32, p.nblk, p.inner, p.inner), "out": Buf(F32, 1, p.inner, 0, "out")}
+
+
+def ref_reduce_blocks(p, v):
+    x, sc = f64(v["x"]), _f32(p.scale)
+    return {"out": expect(sc * x.sum(0, keepdim=True), blocks_chain(p.nblk) * U32 * abs(sc) * x.abs().sum(0, keepdim=True), F32)}
+
+
+def layout_colsum(p):
+    L = {"x": Buf(F16, p.rows, p.cols, p.ldx), "out": Buf(F32, 1, p.cols, 0, "out")}
+    if _ptr(p, "partial"):                                   # the per-block sums: their order is documented, their contents are not an output
+        L["partial"] = Buf(F32, p.nblk, p.cols, p.cols, "scratch")
+    return L
+
+
+def ref_colsum(p, v):
+    """Block b sums the rows [b rpb, (b + 1) rpb) in order, rpb = ceil(rows / nblk) (a block past the last row holds 0); then pv_reduce_blocks' order."""
+    x = f64(v["x"])
+    chain = (p.rows + p.nblk - 1) // p.nblk + blocks_chain(p.nblk)
+    return {"out": expect(x.sum(0, keepdim=True), chain * U32 * x.abs().sum(0, keepdim=True), F32)}
+
+
+def _reduce_scalar(terms, eterm, chain, scale):
+    """scale Sum terms with a per-term relative rounding ``eterm`` (in U32) and the fp32 rounding of the scale itself -> Expect [1, 1]."""
+    mag = terms.abs().sum().reshape(1, 1)
+    return expect(scale * terms.sum().reshape(1, 1), (chain + eterm + 1) * U32 * abs(scale) * mag, F32)
+
+
+def layout_reduce_mean(p):
+    dt = F16 if p.is_f16 else F32
+    L = {"a": Buf(dt, 1, p.n, 0), "out": Buf(F32, 1, 1, 0, "out")}
+    if _ptr(p, "partial"):
+        L["partial"] = Buf(F32, 1, p.n_partial, 0, "scratch")
+    if p.mode == 2:
+        L["b"] = Buf(dt, 1, p.n, 0)
+    return L
+
+
+def ref_reduce_mean(p, v):
+    """mode 0 mean(a), 1 mean|a|, 2 mean((a - b)^2); the scale is the fp32 1 / n (one more rounding)."""
+    a = f64(v["a"])
+    if p.mode == 2:
+        terms, et = (a - f64(v["b"])) ** 2, 3 + 1           # the difference enters squared: twice its rounding, and the product's
+    else:
+        terms, et = (a.abs() if p.mode == 1 else a), 1
+    return {"out": _reduce_scalar(terms, et, mean_chain(p.n, p.n_partial), 1.0 / p.n)}
+
+
+def layout_reduce_sumsq(p):
+    L = {"a": Buf(F32, 1, p.n, 0), "out": Buf(F32, 1, 1, 0, "out")}
+    if _ptr(p, "partial"):
+        L["partial"] = Buf(F32, 1, p.n_partial, 0, "scratch")
+    return L
+
+
+def ref_reduce_sumsq(p, v):
+    return {"out": _reduce_scalar(f64(v["a"]) ** 2, 1, mean_chain(p.n, p.n_partial), _f32(p.scale))}
+
+
+def wgrad_cap(m: int) -> float:
+    """tests/test_hip_kernels.py::test_wgrad_tn's tolerance."""
+    return 2e-6 * max(1.0, math.sqrt(m / 64.0))
+
+
+def layout_wgrad(p):
+    return {"dy": Buf(F16, p.m, p.n, p.lddy), "x": Buf(F16, p.m, p.k, p.ldx), "out": Buf(F32, p.nsplit, p.n * p.k, p.n * p.k, "out")}
+
+
+def ref_wgrad(p, v):
+    """Slab s = dy[rows]^T x[rows] over the rows [s rps, min(m, (s + 1) rps)): an MFMA chain of at most rps products per element."""
+    dy, x = f64(v["dy"]), f64(v["x"])
+    ref, det = [], []
+    for s in range(p.nsplit):
+        r = slice(s * p.rows_per_split, min(p.m, (s + 1) * p.rows_per_split))
+        ref.append((dy[r].T @ x[r]).reshape(-1))
+        det.append(mfma_c(p.rows_per_split) * (dy[r].abs().T @ x[r].abs()).reshape(-1))
+    return {"out": expect(torch.stack(ref), torch.stack(det), F32, cap=wgrad_cap(p.m))}
+
+
+# ===================================================================================================================== the identity loss
+GRAY = (0.2989, 0.5870, 0.1140)
+
+
+def gray_taps(n_in: int, n_out: int, device):
+    """One axis of pv_gray_resize as matrices [n_out, n_in]: C, the bilinear weights of ``bilinear_taps`` (src = max((o + 0.5) in / out - 0.5, 0), i0 =
+    floor, i1 = min(i0 + 1, in - 1), weights 1 - t and t - summed where i1 == i0), and E, the bound of |C' - C| for the weights C' of a kernel that
+    evaluates src in fp32 as the header writes it: the ratio, the product and the difference round (3 U32 of (o + 0.5) in / out + 0.5), and every weight
+    is a hat function of src with slope 1 - continuous over the integer tap boundaries, where the fp32 floor may fall on the other side: the weight that
+    moves to the neighbouring tap is itself below that error.  E holds the error at the taps i0 - 1 .. i0 + 2, the only ones either side can touch."""
+    i0, i1, t = bilinear_taps(n_in, n_out, device)
+    o = torch.arange(n_out, device=device)
+    Cm = torch.zeros(n_out, n_in, dtype=torch.float64, device=device)
+    Cm[o, i0] += 1 - t
+    Cm[o, i1] += t
+    es = U32 * (3 * (o.double() + 0.5) * n_in / n_out + 0.5) + U32             # and the weight's own rounding
+    Em = torch.zeros_like(Cm)
+    for d in (-1, 0, 1, 2):
+        Em[o, (i0 + d).clamp(0, n_in - 1)] = es
+    return Cm, Em
+
+
+def layout_gray_resize(p):
+    return {"x": Buf(F32, p.batch, 3 * p.h * p.w, p.x_image_stride), "y": Buf(F32, 1, p.batch * p.size * p.size, 0, "out")}
+
+
+def ref_gray_resize(p, v):
+    """y = mul bilinear(0.2989 r + 0.5870 g + 0.1140 b) + add.  |C'y G C'x^T - Cy G Cx^T| <= (Cy + Ey) |G| (Cx + Ex)^T - Cy |G| Cx^T for the tap
+    boundaries (``gray_taps``); roundings: the gray value (three fp32 constants, three products, two sums: 8 U32), the two mixes (10), mul and add (2)."""
+    x = f64(v["x"]).reshape(p.batch, 3, p.h, p.w)
+    g = GRAY[0] * x[:, 0] + GRAY[1] * x[:, 1] + GRAY[2] * x[:, 2]
+    ga = GRAY[0] * x[:, 0].abs() + GRAY[1] * x[:, 1].abs() + GRAY[2] * x[:, 2].abs()
+    Cy, Ey = gray_taps(p.h, p.size, x.device)
+    Cx, Ex = gray_taps(p.w, p.size, x.device)
+    mul, add = _f32(p.mul), _f32(p.add)
+    r = Cy @ g @ Cx.T
+    mag = Cy @ ga @ Cx.T
+    tap = (Cy + Ey) @ ga @ (Cx + Ex).T - mag
+    det = abs(mul) * (tap + 18 * U32 * mag) + 2 * U32 * (abs(mul) * mag + abs(add))
+    return {"y": expect((mul * r + add).reshape(1, -1), det.reshape(1, -1), F32, cap=CAP["gray"])}
+
+
+def layout_gray_resize_backward(p):
+    return {"dy": Buf(F32, p.batch, p.size * p.size, p.dy_image_stride), "dx": Buf(F32, 1, p.batch * 3 * p.h * p.w, 0, "out")}
+
+
+def ref_gray_resize_backward(p, v):
+    """dx[b][ch] = GRAY[ch] mul Cy^T dy[b] Cx: a gather per input pixel over the outputs whose taps include it - at most ny nx of them, ny / nx the
+    largest number of outputs one input row / column reaches: the chain; each term two products; then mul and the channel weight."""
+    dy = f64(v["dy"]).reshape(p.batch, p.size, p.size)
+    Cy, Ey = gray_taps(p.h, p.size, dy.device)
+    Cx, Ex = gray_taps(p.w, p.size, dy.device)
+    mul = _f32(p.mul)
+    acc = Cy.T @ dy @ Cx
+    mag = Cy.T @ dy.abs() @ Cx
+    tap = (Cy + Ey).T @ dy.abs() @ (Cx + Ex) - mag
+    chain = int(((Cy + Ey) > 0).sum(0).max().item() * ((Cx + Ex) > 0).sum(0).max().item())
+    det = abs(mul) * (tap + (chain + 6) * U32 * mag)
+    w = torch.tensor(GRAY, dtype=torch.float64, device=dy.device).view(1, 3, 1, 1)
+    return {"dx": expect((w * (mul * acc).unsqueeze(1)).reshape(1, -1), (w * det.unsqueeze(1)).reshape(1, -1), F32, cap=CAP["gray"])}
+
+
+COS_EPS = 1e-8
+
+
+def cosine_parts(p, v):
+    """(cos, its error bound, the sums) of pv_cosine_embedding_loss: cos = ab / sqrt((aa + eps)(cc + eps)), eps = 1e-8; each sum: 64 lanes of
+    ceil(dim / 64) terms, a 6-level tree."""
+    a, c = f64(v["e1"]), f64(v["e2"])
+    ab, aa, cc = (a * c).sum(1, keepdim=True), (a * a).sum(1, keepdim=True) + COS_EPS, (c * c).sum(1, keepdim=True) + COS_EPS
+    chain = (p.dim + 63) // 64 + 6 + 1
+    den = torch.sqrt(aa * cc)
+    cos = ab / den
+    rden = (chain + 4) * U32                              # half of each sum's relative error, the product, the root
+    ecos = chain * U32 * (a * c).abs().sum(1, keepdim=True) / den + cos.abs() * (rden + 4 * U32)
+    return a, c, ab, aa, cc, den, cos, ecos, chain, rden
+
+
+def layout_cosine_loss(p):
+    L = {"e1": Buf(F16, p.batch, p.dim, p.dim), "e2": Buf(F16, p.batch, p.dim, p.dim), "per_sample": Buf(F32, 1, p.batch, 0, "out")}
+    if _ptr(p, "de2"):
+        L["de2"] = Buf(F16, p.batch, p.dim, p.dim, "out")
+    return L
+
+
+def cosine_ambiguous(p, v):
+    """Samples whose max(0, cos) branch the fp32 cosine may take on the other side (target <= 0, |cos| within its error)."""
+    cos, ecos = cosine_parts(p, v)[6:8]
+    return (cos.abs() <= ecos) if _f32(p.target) <= 0 else torch.zeros_like(cos, dtype=torch.bool)
+
+
+def ref_cosine_loss(p, v):
+    """target > 0: 1 - cos; else max(0, cos).  de2 = gscale / batch dloss/dcos (a / den - cos c / (cc + eps)).  A sample whose cosine lies within its own
+    error of 0 may take either branch of the max: its bounds are widened by the branch difference (|cos|, and the whole gradient)."""
+    a, c, ab, aa, cc, den, cos, ecos, chain, rden = cosine_parts(p, v)
+    pos = _f32(p.target) > 0
+    amb = cosine_ambiguous(p, v)
+    loss = 1 - cos if pos else cos.clamp_min(0)
+    eloss = ecos + U32 * (1 + cos.abs()) + amb * cos.abs()
+    res = {"per_sample": expect(loss.reshape(1, -1), eloss.reshape(1, -1), F32)}
+    if "de2" in v:
+        k = _f32(p.gscale) / p.batch
+        dcos = -torch.ones_like(cos) if pos else (cos > 0).double()
+        t1, t2 = a / den, cos * c / cc
+        # a / den carries den's relative error; cos c / cc the cosine's error and the sum's; four divisions / products and the difference round
+        e = t1.abs() * rden + ecos * (c / cc).abs() + t2.abs() * chain * U32 + 8 * U32 * (t1.abs() + t2.abs())
+        grad = k * dcos * (t1 - t2)
+        wide = amb * abs(k) * (t1 - t2).abs()
+        res["de2"] = expect(grad, abs(k) * dcos.abs() * e + 2 * U32 * grad.abs() + wide, F16, cap=CAP["pointwise_bwd"])
+    return res
+
+
+# ===================================================================================================================== LayerNorm backward
+def ln_bwd_chain(cols: int) -> int:
+    """Longest fp32 chain of a row sum of pv_layernorm_backward: a lane adds at most 48 of the row's elements (8 x 6 chunks of the widest vector form; 32
+    in the one-wave-per-row form at 2048 columns), then a tree of at most 6 levels."""
+    return min(cols, 48) + 6
+
+
+def layout_layernorm_backward(p):
+    grp = max(p.dy_group, 1)
+    rpw = max(p.rows_per_wave, 1)
+    L = {"x": Buf(F16, p.rows, p.cols, p.ldx), "dy": Buf(F16, (p.rows - 1) // grp + 1, p.cols, p.lddy), "dx": Buf(F16, p.rows, p.cols, p.lddx, "out"),
+         "gamma": Buf(F32, 1, p.cols, 0), "beta": Buf(F32, 1, p.cols, 0)}
+    if _ptr(p, "dgb_partial"):
+        L["dgb_partial"] = Buf(F32, (p.rows + 4 * rpw - 1) // (4 * rpw), 2 * p.cols, 2 * p.cols, "out")
+    if _ptr(p, "add"):
+        L["add"] = Buf(F16, p.rows, p.cols, p.ldadd)
+    return L
+
+
+def ln_bwd_terms(p, v):
+    """The fp64 quantities of the LayerNorm (+ LeakyReLU) backward and the elements whose LeakyReLU branch fp32 may decide the other way."""
+    if p.act not in (0, 3):
+        raise ValueError(f"pv_layernorm_backward: activation {p.act} (the header: LeakyReLU or none)")
+    x = f64(v["x"])
+    rows, cols = x.shape
+    L = ln_bwd_chain(cols)
+    grp = max(p.dy_group, 1)
+    r = torch.arange(rows, device=x.device)
+    dys = torch.where((r % grp < p.dy_skip) if p.dy_group > 1 else torch.zeros_like(r, dtype=torch.bool), 0.0, _f32(p.dy_scale)).double()[:, None]
+    g0 = f64(v["dy"])[r // grp] * dys
+    gam, bet = f64(v["gamma"]).reshape(1, -1), f64(v["beta"]).reshape(1, -1)
+    mean = x.mean(1, keepdim=True)
+    var = ((x - mean) ** 2).mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + float(p.eps))
+    xh = (x - mean) * rstd
+    # mean: a chain of L on Sum|x| / cols and the division; rstd: half the variance's chain and the squares' roundings, rsqrt's ulp
+    em = (L + 1) * U32 * x.abs().mean(1, keepdim=True)
+    r_rstd = (L / 2 + 6) * U32
+    exh = rstd * (em + U32 * (x.abs() + mean.abs())) + xh.abs() * (r_rstd + U32)
+    z = gam * xh + bet
+    ez = gam.abs() * exh + 2 * U32 * ((gam * xh).abs() + bet.abs())
+    leaky = p.act == 3
+    amb = (z.abs() <= ez) if leaky else torch.zeros_like(z, dtype=torch.bool)
+    g = torch.where(z < 0, 0.01 * g0, g0) if leaky else g0
+    return dict(x=x, L=L, g0=g0, g=g, gam=gam, rstd=rstd, xh=xh, exh=exh, r_rstd=r_rstd, amb=amb)
+
+
+def ref_layernorm_backward(p, v):
+    """y = act(gamma xhat + beta), g = dy[r / dy_group] dy_scale act'(z) (0 on the first dy_skip rows of a group), dxhat = g gamma:
+        dx = rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat)) (+ add);   dgb_partial[block] = (Sum g xhat, Sum g) over the block's 4 rows_per_wave rows.
+    An element whose pre-activation lies within its own fp32 error of 0 may take either LeakyReLU branch: its g moves by 0.99 |g0|, which reaches the
+    element itself, both row means (every element of its row) and its column of the block's partial sums - all widened by exactly that."""
+    t = ln_bwd_terms(p, v)
+    x, L, g, gam, rstd, xh, exh, r_rstd = t["x"], t["L"], t["g"], t["gam"], t["rstd"], t["xh"], t["exh"], t["r_rstd"]
+    rows, cols = x.shape
+    dxh = g * gam
+    edxh = 3 * U32 * dxh.abs()                               # dy dy_scale, the slope, gamma
+    s1, s2 = dxh.mean(1, keepdim=True), (dxh * xh).mean(1, keepdim=True)
+    e1 = (L + 1) * U32 * dxh.abs().mean(1, keepdim=True) + edxh.mean(1, keepdim=True)
+    e2 = (L + 2) * U32 * (dxh * xh).abs().mean(1, keepdim=True) + (dxh.abs() * exh + edxh * xh.abs()).mean(1, keepdim=True)
+    core = rstd * (dxh - s1 - xh * s2)
+    D = 0.99 * (t["g0"] * gam).abs() * t["amb"]
+    wide = rstd * (D + D.mean(1, keepdim=True) + xh.abs() * (D * xh.abs()).mean(1, keepdim=True))
+    err = rstd * (edxh + e1 + exh * s2.abs() + xh.abs() * e2 + 3 * U32 * (dxh.abs() + s1.abs() + (xh * s2).abs())) + core.abs() * (r_rstd + U32) + wide
+    ref = core
+    if "add" in v:
+        ref = core + f64(v["add"])
+        err = err + U32 * (core.abs() + f64(v["add"]).abs())
+    res = {"dx": expect(ref, err, F16, cap=CAP["ln_bwd_dx"])}
+    if "dgb_partial" in v:
+        rpw = max(p.rows_per_wave, 1)
+        blk = 4 * rpw
+        nb = (rows + blk - 1) // blk
+
+        def per_block(q):
+            return torch.cat([q, torch.zeros(nb * blk - rows, cols, dtype=torch.float64, device=x.device)]).reshape(nb, blk, cols).sum(1)
+        Dg = 0.99 * t["g0"].abs() * t["amb"]
+        dg, db = per_block(g * xh), per_block(g)
+        edg = (rpw + 4 + 2) * U32 * per_block((g * xh).abs()) + per_block(g.abs() * exh + Dg * xh.abs())
+        edb = (rpw + 4 + 1) * U32 * per_block(g.abs()) + per_block(Dg)
+        res["dgb_partial"] = expect(torch.cat([dg, db], 1), torch.cat([edg, edb], 1), F32, cap=CAP["ln_bwd_dgb"])
+    return res
+
+
 # ===================================================================================================================== tables
 #: positional argument names of the launchers that take no parameter struct (``_lib.SIGNATURES`` order, stream excluded)
 ARGS = {
@@ -1325,9 +1920,52 @@ ARGS = {
     "pv_patchify": ("x", "out", "batch", "ch", "img", "patch", "kpad"),
     "pv_clip_vision_embed": ("patches", "cls", "pos", "out", "batch", "ntok", "dim"),
     "pv_clip_text_embed": ("ids", "tok", "pos", "concept", "placeholder_idx", "n_concept", "out", "batch", "seq", "dim"),
+    # the training tape
+    "pv_act_forward": ("x", "ldx", "y", "ldy", "rows", "cols", "act"),
+    "pv_act_backward": ("x", "ldx", "dy", "lddy", "dx", "lddx", "rows", "cols", "act"),
+    "pv_geglu": ("x", "ldx", "out", "ldo", "rows", "n"),
+    "pv_geglu_backward": ("h", "ldh", "dy", "lddy", "dh", "lddh", "rows", "n"),
+    "pv_col_affine_f16": ("x", "ldx", "scale", "shift", "y", "ldy", "rows", "cols"),
+    "pv_prelu_f16": ("x", "ldx", "dy", "lddy", "slope", "out", "ldo", "rows", "cols"),
+    "pv_add_rows_f16": ("a", "lda", "b", "ldb", "out", "ldo", "rows", "cols"),
+    "pv_dropout_f16": ("x", "ldx", "out", "ldo", "add", "ldadd", "rows", "cols", "copies", "p", "rng", "site", "backward"),
+    "pv_softmax_rows_backward": ("p", "ldp", "dp", "lddp", "rows", "cols", "scale"),
+    "pv_transpose_f16": ("x", "ldx", "rows", "cols", "out", "ldo", "rows_pad"),
+    "pv_dilate2x": ("x", "ldx", "z", "batch", "h", "w", "c"),
+    "pv_pool2x_sum": ("g", "add", "ldadd", "out", "batch", "h", "w", "c"),
+    "pv_maxpool2x2": ("x", "dy", "out", "batch", "h", "w", "c"),
+    "pv_sign_f32": ("x", "coef", "out", "n"),
+    "pv_clamp_mask_f32": ("y", "dy", "lo", "hi", "out", "n"),
+    "pv_gather_rows_f32": ("x", "ldx", "idx", "out", "batch", "seq", "n_e", "dim", "scale"),
+    "pv_reduce_blocks": ("x", "nblk", "inner", "scale", "out"),
+    "pv_colsum_f16": ("x", "ldx", "rows", "cols", "partial", "nblk", "out"),
+    "pv_reduce_mean": ("a", "b", "mode", "is_f16", "n", "partial", "n_partial", "out"),
+    "pv_reduce_sumsq": ("a", "n", "scale", "partial", "n_partial", "out"),
+    "pv_wgrad_tn": ("dy", "lddy", "x", "ldx", "m", "n", "k", "out", "nsplit", "rows_per_split"),
+    "pv_gray_resize": ("x", "x_image_stride", "y", "batch", "h", "w", "size", "mul", "add"),
+    "pv_gray_resize_backward": ("dy", "dy_image_stride", "dx", "batch", "h", "w", "size", "mul"),
+    "pv_cosine_embedding_loss": ("e1", "e2", "batch", "dim", "target", "gscale", "per_sample", "de2"),
+}
+
+#: the training tape's single launches (tests/test_abi_ref_cpu.py: none of them may leave ``REF`` again): launcher -> (layout, reference, helpers)
+TRAINING = {
+    "pv_act_forward": (layout_act_forward, ref_act_forward), "pv_act_backward": (layout_act_backward, ref_act_backward),
+    "pv_geglu": (layout_geglu, ref_geglu), "pv_geglu_backward": (layout_geglu_backward, ref_geglu_backward),
+    "pv_col_affine_f16": (layout_col_affine, ref_col_affine), "pv_prelu_f16": (layout_prelu, ref_prelu),
+    "pv_add_rows_f16": (layout_add_rows, ref_add_rows), "pv_dropout_f16": (layout_dropout, ref_dropout),
+    "pv_softmax_rows_backward": (layout_softmax_rows_backward, ref_softmax_rows_backward), "pv_transpose_f16": (layout_transpose, ref_transpose),
+    "pv_dilate2x": (layout_dilate, ref_dilate), "pv_pool2x_sum": (layout_pool2x, ref_pool2x), "pv_maxpool2x2": (layout_maxpool, ref_maxpool),
+    "pv_sign_f32": (layout_sign, ref_sign), "pv_clamp_mask_f32": (layout_clamp_mask, ref_clamp_mask),
+    "pv_gather_rows_f32": (layout_gather_rows, ref_gather_rows), "pv_reduce_blocks": (layout_reduce_blocks, ref_reduce_blocks),
+    "pv_colsum_f16": (layout_colsum, ref_colsum), "pv_reduce_mean": (layout_reduce_mean, ref_reduce_mean),
+    "pv_reduce_sumsq": (layout_reduce_sumsq, ref_reduce_sumsq), "pv_wgrad_tn": (layout_wgrad, ref_wgrad),
+    "pv_gray_resize": (layout_gray_resize, ref_gray_resize), "pv_gray_resize_backward": (layout_gray_resize_backward, ref_gray_resize_backward),
+    "pv_cosine_embedding_loss": (layout_cosine_loss, ref_cosine_loss, cosine_parts),
+    "pv_layernorm_backward": (layout_layernorm_backward, ref_layernorm_backward, ln_bwd_terms),
 }
 
 LAYOUT = {
+    **{n: f[0] for n, f in TRAINING.items()},
     "pv_gemm_conv": layout_gemm, "pv_attention": layout_attention, "pv_cross_attention": layout_xattn,
     "pv_cross_attention_lnq": layout_xattn_lnq, "pv_cross_attention_fused": layout_xattn_fused, "pv_xattn_pack_kv": layout_pack_kv,
     "pv_row_gemm": layout_row_gemm, "pv_layernorm": layout_layernorm, "pv_groupnorm_stats": layout_gn_stats,
@@ -1343,6 +1981,7 @@ LAYOUT = {
 }
 
 REF = {
+    **{n: f[1] for n, f in TRAINING.items()},
     "pv_gemm_conv": ref_gemm, "pv_attention": ref_attention, "pv_cross_attention": ref_xattn, "pv_cross_attention_lnq": ref_xattn_lnq,
     "pv_cross_attention_fused": ref_xattn_fused, "pv_xattn_pack_kv": ref_pack_kv, "pv_row_gemm": ref_row_gemm, "pv_layernorm": ref_layernorm,
     "pv_groupnorm_stats": ref_gn_stats, "pv_groupnorm_stats_from_colstats": ref_gn_stats, "pv_groupnorm_scale_shift": ref_gn_scale_shift,
@@ -1370,21 +2009,25 @@ DEPENDENT = {
     "pv_clip_text_embed": ("ids", "tok", lambda p, ids: Buf(F32, int(ids.max().item()) + 1, p.dim, p.dim), 0),
 }
 
-_BWD = "backward / training launcher: the training tape's audit is a separate piece of work"
-_OPT = "optimizer launcher: outside the inference audit"
 _QUERY = "a host-side query: launches nothing"
+_TABLE = ("its operands are reached through a device table of pointers (%s), which the Auditor cannot resolve to held tensors yet; "
+          "tests/test_hip_kernels.py tests it directly (%s)")
 #: every other symbol of ``photoverse_amd._lib.SIGNATURES``: deliberately outside the launch audit, and why.  A launcher is in exactly one of REF and
 #: this table (tests/test_abi_ref_cpu.py); nothing a plan of ``run_inference`` / ``generate.py`` can record may be listed here.
 NOT_AUDITED = {
     "pv_abi_version": _QUERY, "pv_device_count": _QUERY, "pv_xattn_fused_wo_slot": _QUERY,
     "pv_gemm_conv_kernel_info": _QUERY + " (the dispatch rule the edge catalogue asks)", "pv_attention_kernel_info": _QUERY + " (the dispatch rule the edge catalogue asks)",
-    **{n: _BWD for n in ("pv_cross_attention_backward", "pv_transpose_f16", "pv_layernorm_backward", "pv_reduce_blocks", "pv_colsum_f16", "pv_attention_backward",
-                         "pv_groupnorm_backward", "pv_geglu_backward", "pv_act_backward", "pv_add_rows_f16", "pv_dilate2x", "pv_pool2x_sum", "pv_dropout_f16",
-                         "pv_gray_resize_backward", "pv_wgrad_tn", "pv_softmax_rows_backward", "pv_clamp_mask_f32", "pv_sign_f32", "pv_gather_rows_f32",
-                         "pv_pack_weights")},
-    **{n: "forward launcher of the training tape / the face-identity loss only (no inference plan records it): " + _BWD
-       for n in ("pv_geglu", "pv_act_forward", "pv_col_affine_f16", "pv_prelu_f16", "pv_maxpool2x2", "pv_gray_resize", "pv_cosine_embedding_loss", "pv_reduce_mean")},
-    **{n: _OPT for n in ("pv_reduce_sumsq", "pv_sumsq_multi", "pv_clip_coef_groups", "pv_adamw_multi")},
+    "pv_attention_backward": "a multi-kernel MFMA backward pass (the delta pass, dq, dk / dv): the bounds of its fp16 P / dS intermediates through three "
+                             "products need their own derivation - the next slice of the training audit",
+    "pv_cross_attention_backward": "a multi-kernel MFMA backward pass (dq, the dK / dV partials per 512-query chunk, their ordered reduce) over two "
+                                   "softmaxes and the to_v_ip_norm gradient: its bounds need their own derivation - the next slice of the training audit",
+    "pv_groupnorm_backward": "three kernels (partial sums, their reduce, the apply pass) whose group sums cancel: the bound of (dxhat - m1 - xhat m2) over "
+                             "hw x C/G terms needs its own derivation - the next slice of the training audit",
+    "pv_pack_weights": _TABLE % ("entries: int64 [E][9] with src / dst / dstT addresses", "test_pack_weights_multi"),
+    "pv_sumsq_multi": _TABLE % ("entries: int64 [T][6] with the gradient addresses", "the multi-tensor optimizer tests"),
+    "pv_clip_coef_groups": "reads the partial sums pv_sumsq_multi wrote for a pointer table and updates the overflow counters in place: audited with "
+                           "pv_sumsq_multi once the Auditor resolves pointer tables; the multi-tensor optimizer tests cover it",
+    "pv_adamw_multi": _TABLE % ("entries: int64 [T][6] with parameter, gradient and moment addresses, updated in place", "the multi-tensor optimizer tests"),
 }
 
 #: struct fields no layout / reference reads, and why.  Every other field of an audited struct is read by its layout or its reference
@@ -1406,6 +2049,7 @@ STRUCT_FUNCS = {
     "LayerNormParams": (layout_layernorm, ref_layernorm),
     "GroupNormParams": (layout_groupnorm, layout_gn_stats, layout_gn_scale_shift, layout_gn_apply, group_stats, ref_gn_stats, ref_gn_scale_shift,
                         ref_gn_apply),
+    "LayerNormBwdParams": TRAINING["pv_layernorm_backward"],
 }
 
 
@@ -1418,6 +2062,7 @@ ARG_FUNCS = {
     "pv_cast_f32_to_f16": (layout_cast_to_f16, ref_cast_to_f16), "pv_cast_f16_to_f32": (layout_cast_to_f32, ref_cast_to_f32),
     "pv_patchify": (layout_patchify, ref_patchify), "pv_clip_vision_embed": (layout_vision_embed, ref_vision_embed),
     "pv_clip_text_embed": (layout_text_embed, ref_text_embed),
+    **{n: f for n, f in TRAINING.items() if n in ARGS},
 }
 
 

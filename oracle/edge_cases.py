@@ -18,6 +18,11 @@ fp32 pointwise ones, ``pv_rows_mean``, the casts, patchify and the two embeds) a
 (name prefix ``product-``) runs single launches of them at the shapes the product gives them.  A case may promise that two of its launches are the
 same kernel on the same inputs (``rec.same_bits``: pairs of outputs that must agree bit for bit - the launchers' documented substitutions).
 
+A third group (prefix ``train-``) holds single launches of 25 launchers of the training tape - pointwise passes and their backwards, dropout, the layout
+and exact-select launchers, the fixed-order reductions, the pieces of the identity loss, ``pv_layernorm_backward``, ``pv_wgrad_tn`` - at the smallest
+shapes that reach their edges (a last 8-column chunk, a tail row, a second workgroup, every threshold of a dispatch from both sides, a one-row last
+slab); no training plan is replayed.
+
 With a CPU device the recorder is dry: it builds the same parameter blocks and tags (the ``*_kernel_info`` calls need no GPU) and never runs.
 """
 from __future__ import annotations
@@ -1005,6 +1010,319 @@ def _text_embed(c):
 
 
 add("clip-text-embed-seq77-concepts-0-1-2", _text_embed)
+
+
+# ============================================================================================================================== the training tape
+# Single launches of the training tape's pointwise, reduction and weight-gradient launchers (no training plan is replayed).  The recorder's methods hand
+# out contiguous outputs, so most launches are recorded directly: every operand that takes a leading dimension gets ld = cols + 8.
+#: rows x cols of the launchers that walk 8-column chunks, 256 chunks a workgroup: one chunk; 165 chunks (no multiple of 256); 325 (a second workgroup)
+PW_SHAPES = ((1, 8), (33, 40), (65, 40))
+TRAIN_RNG = (0x9E3779B9, 0xDEADBEEF, 0x80000007)
+
+
+def _dp(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _ld(t):
+    return t.stride(0) if t is not None else 0
+
+
+def _xz(c, rows, cols, scale=2.0):
+    """fp16 rows with exact zeros (and a negative zero) among them: the x > 0 branches of LeakyReLU / PReLU at 0."""
+    t = c.randn(rows, cols, scale=scale)
+    t.view(-1)[::7] = 0.0
+    t.view(-1)[3::11] = -0.0
+    return c.put(t.to(F16), cols + 8)
+
+
+def _act_cases(c, backward):
+    lib = c.rec.lib
+    for rows, cols in PW_SHAPES:
+        for act in range(5):
+            x = _xz(c, rows, cols)
+            if backward:
+                dy, dx = c.h(rows, cols), c.out(rows, cols, gap=16)
+                c.rec._add(lib.pv_act_backward, _dp(x), _ld(x), _dp(dy), _ld(dy), _dp(dx), _ld(dx), rows, cols, act)
+            else:
+                y = c.out(rows, cols, gap=16)
+                c.rec._add(lib.pv_act_forward, _dp(x), _ld(x), _dp(y), _ld(y), rows, cols, act)
+
+
+add("train-act-forward-every-activation", lambda c: _act_cases(c, False))
+add("train-act-backward-every-activation", lambda c: _act_cases(c, True))
+
+
+def _geglu_cases(c, backward):
+    lib = c.rec.lib
+    for rows, n in PW_SHAPES:
+        h = c.h(rows, 2 * n, scale=2.0)
+        if backward:
+            dy, dh = c.h(rows, n), c.out(rows, 2 * n, gap=16)
+            c.rec._add(lib.pv_geglu_backward, _dp(h), _ld(h), _dp(dy), _ld(dy), _dp(dh), _ld(dh), rows, n)
+        else:
+            out = c.out(rows, n)
+            c.rec._add(lib.pv_geglu, _dp(h), _ld(h), _dp(out), _ld(out), rows, n)
+
+
+add("train-geglu", lambda c: _geglu_cases(c, False))
+add("train-geglu-backward", lambda c: _geglu_cases(c, True))
+
+
+def _add_rows_cases(c):
+    for rows, cols in PW_SHAPES:
+        a = c.randn(rows, cols)
+        b = c.randn(rows, cols)
+        b.view(-1)[::3] *= 2.0 ** -14                        # exponents 14 and more apart: the fp32 sum itself rounds
+        a.view(-1)[1::5] *= 1000.0
+        a, b, out = c.put(a.to(F16), cols + 8), c.put(b.to(F16), cols + 16), c.out(rows, cols)
+        c.rec._add(c.rec.lib.pv_add_rows_f16, _dp(a), _ld(a), _dp(b), _ld(b), _dp(out), _ld(out), rows, cols)
+
+
+add("train-add-rows", _add_rows_cases)
+
+
+def _col_affine_cases(c):
+    for rows, cols in PW_SHAPES:
+        for shift in (False, True):
+            x, y = c.h(rows, cols), c.out(rows, cols)
+            c.rec._add(c.rec.lib.pv_col_affine_f16, _dp(x), _ld(x), _dp(c.f(cols, scale=0.3, shift=1.0)), _dp(c.f(cols) if shift else None), _dp(y), _ld(y), rows, cols)
+
+
+add("train-col-affine-with-and-without-shift", _col_affine_cases)
+
+
+def _prelu_cases(c):
+    slope = c.put(torch.tensor([0.3]))                          # no dyadic value: the product rounds in fp32
+    for rows, cols in PW_SHAPES:
+        for backward in (False, True):
+            x, out = _xz(c, rows, cols), c.out(rows, cols)
+            dy = c.h(rows, cols, gap=16) if backward else None
+            c.rec._add(c.rec.lib.pv_prelu_f16, _dp(x), _ld(x), _dp(dy), _ld(dy), _dp(slope), _dp(out), _ld(out), rows, cols)
+
+
+add("train-prelu-forward-and-backward", _prelu_cases)
+
+
+def _softmax_bwd_cases(c):
+    for rows, cols in PW_SHAPES:
+        pm = c.put(torch.softmax(c.randn(rows, cols, scale=2.0), 1).to(F16), cols + 8)
+        dp = c.h(rows, cols, gap=16)
+        c.rec._add(c.rec.lib.pv_softmax_rows_backward, _dp(pm), _ld(pm), _dp(dp), _ld(dp), rows, cols, 0.3)
+
+
+add("train-softmax-rows-backward", _softmax_bwd_cases)
+
+
+def _dropout(c, x, rows, cols, copies, p, backward, add_t=None, site=5, rng=None):
+    rng = c.put(_i32(TRAIN_RNG)) if rng is None else rng
+    out = c.out(rows, cols if backward else copies * cols)
+    c.rec._add(c.rec.lib.pv_dropout_f16, _dp(x), _ld(x), _dp(out), _ld(out), _dp(add_t), _ld(add_t), rows, cols, copies, float(p), _dp(rng), site, int(backward))
+    return out
+
+
+def _dropout_cases(c):
+    for (rows, cols), p, copies in zip(PW_SHAPES * 2, (0.0, 0.1, 0.0, 0.1, 0.0, 0.1), (1, 3, 3, 1, 3, 3)):
+        _dropout(c, c.h(rows, cols), rows, cols, copies, p, False)
+        _dropout(c, c.h(rows, copies * cols), rows, cols, copies, p, True)
+        _dropout(c, c.h(rows, copies * cols), rows, cols, copies, p, True, add_t=c.h(rows, cols, gap=16))
+
+
+def _dropout_masks(c):
+    """p = 0.5 (a scale of exactly 2) on all-ones: the backward of ones is 2 x the number of kept copies, and so is the sum over the copies (a p = 0
+    backward: keep everything, scale 1) of the forward's own output - every value a small even integer, exact in fp16: the two agree bit for bit."""
+    rows, cols, copies = 33, 40, 3
+    rng = c.put(_i32(TRAIN_RNG))
+    fwd = _dropout(c, c.put(torch.ones(rows, cols, dtype=F16), cols + 8), rows, cols, copies, 0.5, False, rng=rng)
+    bwd = _dropout(c, c.put(torch.ones(rows, copies * cols, dtype=F16), copies * cols + 8), rows, cols, copies, 0.5, True, rng=rng)
+    total = _dropout(c, fwd, rows, cols, copies, 0.0, True, rng=rng)
+    c.rec.same_bits = [(bwd, total)]
+
+
+add("train-dropout-p-copies-forward-backward-add", _dropout_cases)
+add("train-dropout-backward-is-the-sum-of-the-forward-masks", _dropout_masks)
+
+
+def _maxpool_cases(c):
+    for batch, h, w, ch in ((1, 2, 2, 8), (2, 4, 6, 16)):
+        for backward in (False, True):
+            x = c.put((torch.randint(0, 3, (batch * h * w, ch), generator=c.g) * 0.5 - 0.5).to(F16))          # three values: ties in most windows
+            dy = c.put(c.randn(batch * (h // 2) * (w // 2), ch).to(F16)) if backward else None
+            out = c.out(batch * h * w if backward else batch * (h // 2) * (w // 2), ch, gap=0)
+            c.rec._add(c.rec.lib.pv_maxpool2x2, _dp(x), _dp(dy), _dp(out), batch, h, w, ch)
+
+
+add("train-maxpool2x2-ties", _maxpool_cases)
+
+
+def _dilate_pool_cases(c):
+    B, h, w = 2, 3, 5
+    for ch in (8, 24):
+        x, z = c.h(B * h * w, ch), c.out(B * 4 * h * w, ch, gap=0)
+        c.rec._add(c.rec.lib.pv_dilate2x, _dp(x), _ld(x), _dp(z), B, h, w, ch)
+        for with_add in (False, True):
+            g, ad = c.put(c.randn(B * 4 * h * w, ch).to(F16)), (c.h(B * h * w, ch) if with_add else None)
+            c.rec._add(c.rec.lib.pv_pool2x_sum, _dp(g), _dp(ad), _ld(ad), _dp(c.out(B * h * w, ch, gap=0)), B, h, w, ch)
+
+
+add("train-dilate2x-pool2x-3x5", _dilate_pool_cases)
+
+
+def _gather_cases(c):
+    B, seq, n_e, dim = 3, 7, 3, 264
+    x = c.h(B * seq, dim)
+    idx = c.put(torch.tensor([seq - 1, -1, 2], dtype=I32))       # the rows behind seq - 1 and the row in front of 0 are outside their sample: 0
+    c.rec._add(c.rec.lib.pv_gather_rows_f32, _dp(x), _ld(x), _dp(idx), _dp(c.out_flat(B * n_e * dim)), B, seq, n_e, dim, 0.5)
+    x1 = c.h(2 * seq, 8)
+    c.rec._add(c.rec.lib.pv_gather_rows_f32, _dp(x1), _ld(x1), _dp(c.put(torch.tensor([0, seq - 1], dtype=I32))), _dp(c.out_flat(2 * 8)), 2, seq, 1, 8, 1.0)
+
+
+add("train-gather-rows-outside-rows", _gather_cases)
+
+
+def _sign_clamp_cases(c):
+    for n in (1, 257):
+        x = c.randn(n)
+        x[:4] = torch.tensor([0.0, -0.0, 1.0, -1.0])[:n]
+        c.rec.sign(c.put(x), 0.25)
+        y = c.randn(n) * 1.5
+        y[:5] = torch.tensor([-1.0, 1.0, 0.0, -1.0000001, 0.99999994])[:n]       # exactly lo and hi (outside), 0, and their fp32 neighbours
+        c.rec.clamp_mask(c.put(y), c.f(n), -1.0, 1.0)
+
+
+add("train-sign-clamp-mask-n1-n257", _sign_clamp_cases)
+
+
+def _transpose_cases(c):
+    for rows, cols, rp, ldo in ((33, 40, 64, 64), (7, 8, 7, 7), (33, 40, 33, 48)):
+        x, out = c.h(rows, cols), c.out(cols, rp, gap=ldo - rp)
+        c.rec._add(c.rec.lib.pv_transpose_f16, _dp(x), _ld(x), rows, cols, _dp(out), ldo, rp)
+
+
+add("train-transpose-rows-pad", _transpose_cases)
+
+
+def _reduce_blocks_cases(c):
+    for nblk in (1, 7, 8, 9, 31, 32, 33, 57):
+        for inner in (1, 33):
+            c.rec._add(c.rec.lib.pv_reduce_blocks, _dp(c.put(c.randn(nblk, inner))), nblk, inner, 0.25, _dp(c.out_flat(inner)))
+
+
+add("train-reduce-blocks-both-unroll-tails", _reduce_blocks_cases)
+
+
+def _colsum_cases(c):
+    c.rec.colsum(c.h(130, 257))
+    x = c.h(5, 8)
+    c.rec._add(c.rec.lib.pv_colsum_f16, _dp(x), _ld(x), 5, 8, _dp(c.out_flat(4 * 8)), 4, _dp(c.out_flat(8)))       # rows_per_block 2: block 3 owns no row
+
+
+add("train-colsum-130x257-and-an-empty-block", _colsum_cases)
+
+
+def _reduce_mean_cases(c):
+    for n in (1, 255, 4097):                                     # 4097: two partials of 256 threads, a grid-stride loop of nine trips
+        for dt in (F32, F16):
+            for mode in ("mean", "abs", "mse"):
+                a = c.put((c.randn(n) + 0.25).to(dt))
+                c.rec.reduce_mean(a, c.put(c.randn(n).to(dt)) if mode == "mse" else None, mode=mode, out=c.out_flat(1))
+        c.rec.reduce_sumsq(c.f(n), out=c.out_flat(1), scale=0.5)
+
+
+add("train-reduce-mean-sumsq-modes-types-n", _reduce_mean_cases)
+
+
+def _gray_cases(c):
+    B = 2
+    for h, w, S in ((5, 5, 8), (9, 9, 4), (6, 6, 6), (7, 5, 4)):
+        x = c.put(c.randn(B, 3 * h * w), 3 * h * w + 8)           # an image stride larger than the image
+        c.rec._add(c.rec.lib.pv_gray_resize, _dp(x), _ld(x), _dp(c.out_flat(B * S * S)), B, h, w, S, 0.5, -1.0)
+        dy = c.put(c.randn(B, S * S), 3 * S * S)                  # channel 0 of a 3-channel buffer
+        c.rec._add(c.rec.lib.pv_gray_resize_backward, _dp(dy), _ld(dy), _dp(c.out_flat(B * 3 * h * w)), B, h, w, S, 0.5)
+
+
+add("train-gray-resize-and-backward", _gray_cases)
+
+
+def _cosine_cases(c):
+    B = 3
+    for dim in (8, 100, 512):
+        for target in (1.0, -1.0):
+            for grad in (False, True):
+                e1 = c.randn(B, dim)
+                e2 = 0.9 * e1 + 0.3 * c.randn(B, dim)              # cosines near +-0.95: far from the max(0, cos) branch point
+                e2[1] = -e2[1]
+                ls, de2 = c.out_flat(B), (c.out(B, dim, gap=0) if grad else None)
+                c.rec._add(c.rec.lib.pv_cosine_embedding_loss, _dp(c.put(e1.to(F16))), _dp(c.put(e2.to(F16))), B, dim, target, 4.0, _dp(ls), _dp(de2))
+
+
+add("train-cosine-embedding-loss-dims-targets", _cosine_cases)
+
+
+def _ln_bwd(c, rows, cols, *, act=0, affine=False, rpw=1, ldx=None, with_add=False, dy_group=1, dy_skip=0, dy_scale=1.0):
+    from photoverse_amd._lib import LayerNormBwdParams
+    gap = 8 if cols % 8 == 0 else 4
+    x = c.put((c.randn(rows, cols) * 1.5 + 0.3).to(F16), ldx or cols + gap)
+    dy = c.put(c.randn((rows - 1) // max(dy_group, 1) + 1, cols).to(F16), cols + 2 * gap)
+    dx = c.out(rows, cols, gap=gap)
+    gam, bet = c.f(cols, scale=0.2, shift=1.0), c.f(cols, scale=0.1)
+    ad = c.put(c.randn(rows, cols).to(F16), cols + 2 * gap) if with_add else None
+    nblk = (rows + 4 * rpw - 1) // (4 * rpw)
+    part = c.out(nblk, 2 * cols, F32, gap=0) if affine else None
+    p = LayerNormBwdParams(_dp(x), _ld(x), _dp(dy), _ld(dy), _dp(dx), _ld(dx), _dp(gam), _dp(bet), _dp(part), rows, cols, 1e-5, act, dy_group, dy_skip, dy_scale, rpw,
+                           _dp(ad), _ld(ad))
+    c.rec._add(c.rec.lib.pv_layernorm_backward, p)
+    return part, nblk
+
+
+def ln_bwd_full_workgroup(cols: int) -> int:
+    """Rows of one workgroup of the vector form the launcher picks for ``cols``: 4 waves of 64 / LPR rows (the header's dispatch by cols / 8)."""
+    nch = cols // 8
+    lpr = 8 if nch <= 40 else 16 if nch <= 96 else 32 if nch <= 160 else 64
+    return 4 * 64 // lpr
+
+
+#: both sides of every threshold of the vector dispatch, its narrowest and widest rows, and a width inside the first instantiation
+LN_BWD_COLS = (8, 200, 320, 328, 640, 648, 768, 776, 1024, 1032, 1280, 1288, 2048)
+
+
+def _ln_bwd_vector(c):
+    for i, cols in enumerate(LN_BWD_COLS):
+        _ln_bwd(c, ln_bwd_full_workgroup(cols) + 1, cols, act=3 if i % 2 == 0 else 0, with_add=i % 3 == 0)
+
+
+def _ln_bwd_scalar_affine(c):
+    _ln_bwd(c, 5, 324, act=3)                                    # no multiple of 8: the one-wave-per-row kernel
+    _ln_bwd(c, 5, 320, act=0, ldx=321, with_add=True)            # a row stride that is no multiple of 8
+    part, nblk = _ln_bwd(c, 9, 40, act=3, affine=True)           # rows_per_wave 1: two blocks and one row
+    c.rec._add(c.rec.lib.pv_reduce_blocks, _dp(part), nblk, 2 * 40, 1.0, _dp(c.out_flat(2 * 40)))
+    _ln_bwd(c, 2053, 8, act=3, affine=True, rpw=2, with_add=True)       # rows_per_wave 2: 256 blocks of 8 rows and one of 5
+    _ln_bwd(c, 7, 200, act=0, affine=True)
+
+
+def _ln_bwd_grouped(c):
+    _ln_bwd(c, 33, 320, act=3, dy_group=5, dy_skip=1, dy_scale=0.25)                       # a vector instantiation; the last group has three rows
+    _ln_bwd(c, 33, 40, act=3, affine=True, dy_group=5, dy_skip=1, dy_scale=0.25, with_add=True)
+
+
+add("train-layernorm-backward-vector-thresholds", _ln_bwd_vector)
+add("train-layernorm-backward-scalar-and-affine", _ln_bwd_scalar_affine)
+add("train-layernorm-backward-dy-group-skip-scale", _ln_bwd_grouped)
+
+
+def _wgrad_cases(c):
+    """The launch pair ``Recorder.wgrad`` records (the slabs, then their pv_reduce_blocks with the scale), with the slab height given: 64-row slabs for the
+    small shapes; (1025, 8, 136) in slabs of 1024 rows: two slabs, the last one of a single row."""
+    for m, n, k, rps in ((7, 8, 8, 64), (65, 136, 200, 64), (1025, 8, 136, 1024)):
+        dy = c.put(c.randn(m, n + 8).to(F16), n + 16)[:, 8:]     # a column slice: the row gap holds NaN behind it and 8 live columns in front
+        x = c.h(m, k)
+        nsplit = (m + rps - 1) // rps
+        part = c.rec.empty((nsplit, n, k), F32)
+        c.rec._add(c.rec.lib.pv_wgrad_tn, _dp(dy), _ld(dy), _dp(x), _ld(x), m, n, k, _dp(part), nsplit, rps, tag=("pv_wgrad_tn", 0.0, 0.0))
+        c.rec._add(c.rec.lib.pv_reduce_blocks, _dp(part), nsplit, n * k, 0.5, _dp(c.out_flat(n * k)))
+
+
+add("train-wgrad-tn-slabs-and-their-sum", _wgrad_cases)
 
 
 #: Instantiations no argument and no per-call switch can select: the only symbols the dispatch sweep may leave unaudited

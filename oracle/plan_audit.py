@@ -176,6 +176,17 @@ def _flags(name, p) -> str:
     if name in ("pv_cfg_dpm_step_guided", "pv_cfg_dpm_step_stochastic", "pv_cfg_dpm_step_pag"):
         three, pag = A.step_reads(p)
         return " ".join(k for k, c in (("three-forward", three), ("pag", pag), ("rescale", p.rescale > 0), ("mask", g("mask")), ("rng", g("rng"))) if c)
+    if name in A.TRAINING:
+        f = [f"act={A.ACT_NAMES.get(p.act, p.act)}"] if name in ("pv_act_forward", "pv_act_backward", "pv_layernorm_backward") else []
+        f += [k for k in ("backward", "add", "shift", "dy", "de2", "dgb_partial", "is_f16") if g(k) and not (k == "dy" and name not in ("pv_prelu_f16", "pv_maxpool2x2"))]
+        f += [f"{k}={g(k)}" for k in ("copies", "mode", "nsplit", "rows_per_wave", "dy_group", "n_e") if g(k) and (k != "copies" or g(k) > 1)]
+        if name == "pv_layernorm_backward":
+            f.append("vector" if not g("dgb_partial") and p.cols % 8 == 0 and (p.ldx | p.lddy | p.lddx | (p.ldadd if g("add") else 0)) % 8 == 0 else "scalar")
+        if name == "pv_dropout_f16":
+            f.append(f"p={p.p:g}")
+        if name == "pv_cosine_embedding_loss":
+            f.append(f"target={p.target:g}")
+        return " ".join(f)
     keys = {"pv_freeu_rows": ("x", "skip"), "pv_resize_bilinear_affine_f32": ("ca", "y"), "pv_affine_rows_f32": ("y",), "pv_rows_mean": ("accumulate",),
             "pv_clip_text_embed": ("n_concept",),
             "pv_attention": ("causal", "lse"), "pv_cross_attention": ("vnorm", "fusion"), "pv_cross_attention_lnq": ("ln", "vnorm", "fusion"),

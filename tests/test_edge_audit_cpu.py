@@ -268,3 +268,42 @@ def test_lnq_rejects_widths_its_gemm_cannot_walk(E):
         with E.environment({}):
             p = E.build(E.by_name(rec_case)).calls[0][1][0]._obj
         assert p.heads * p.d == 320
+
+
+# ------------------------------------------------------------------------------------------------------------------ the training tape's cases
+def test_training_cases_give_every_leading_dimension_a_row_gap(E, recorded):
+    """Every leading dimension a launch of a ``train-`` case passes is larger than the width of the buffer it strides (a kernel that took cols for ld,
+    or wrote into the gap, would otherwise go unseen); the only contiguous ones are the two ``ldo == rows_pad`` transposes the catalogue asks for."""
+    import ctypes as C
+    seen = set()
+    for name, rec in recorded.items():
+        if not name.startswith("train-"):
+            continue
+        for fn, args in rec.calls:
+            launcher, p, struct = E._call_params(fn, args)
+            L = A.LAYOUT[launcher](p)
+            names = [n for n, _ in type(struct)._fields_] if struct is not None else list(A.ARGS[launcher])
+            for k in names:
+                if not (k.startswith("ld") or k.endswith("_image_stride")) or not getattr(p, k):
+                    continue
+                val = getattr(p, k)
+                strided = [b for b in L.values() if b is not None and b.ld == val]
+                assert strided, (name, launcher, k)
+                if launcher == "pv_transpose_f16" and k == "ldo" and p.ldo == p.rows_pad:
+                    continue
+                assert any(val > b.cols for b in strided), (name, launcher, k, val)      # (another buffer of the launch may share the value as its width)
+                seen.add((launcher, k))
+    assert {l for l, _ in seen} == {l for l in A.TRAINING if any(k.startswith("ld") or k.endswith("_image_stride") for k in A.ARGS.get(l, ("ldx",)))}
+
+
+def test_training_cases_are_dry_recorded_with_flags_that_tell_their_variants_apart(E, recorded):
+    """The coverage table's flags: the activation, forward / backward, the optional operands, the kernel form of pv_layernorm_backward."""
+    flags = {}
+    for name, rec in recorded.items():
+        if name.startswith("train-"):
+            for fn, args in rec.calls:
+                launcher, p, _ = E._call_params(fn, args)
+                flags.setdefault(launcher, set()).add(PA._flags(launcher, p))
+    assert {f.split()[0] for f in flags["pv_act_backward"]} == {"act=none", "act=silu", "act=quick-gelu", "act=leaky-relu", "act=gelu"}
+    assert any("vector" in f for f in flags["pv_layernorm_backward"]) and any("scalar" in f and "dgb_partial" in f for f in flags["pv_layernorm_backward"])
+    assert len(flags["pv_dropout_f16"]) >= 10 and len(flags["pv_reduce_mean"]) == 6 and flags["pv_prelu_f16"] == {"", "dy"}

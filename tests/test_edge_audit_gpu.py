@@ -8,9 +8,13 @@ Since the newer loop features and the pre-loop conditioning joined the catalogue
 launchers, ``pv_rows_mean``, the casts, patchify, the two embeds, ``pv_fusion_draw``; 51 cases, 345 launches, a group of them at the product's shapes) a case
 may also name pairs of outputs that must agree bit for bit (the launchers' documented substitutions).
 
-Wall time of this file alone on one MI355X: 7.19 s for its 178 tests (5.2 s of it in the audits, 522 launches; every one of the 51 newer cases below 0.1 s);
-the parent commit's file on the same box, same visit: 7.03 s for 127 tests (177 launches); the whole GPU suite then: 231.0 s for 573 tests (EXPERIMENTS.md,
-"Edge audit")."""
+The 24 ``train-`` cases (180 launches) are single launches of 25 launchers of the training tape - the pointwise fp16 passes and their backwards, dropout, the
+layout and exact-select launchers, the fixed-order reductions, the pieces of the identity loss, ``pv_layernorm_backward``, ``pv_wgrad_tn`` with its slab sum -
+through the same ``test_edge_case`` with no tolerance of their own; no training plan is replayed.
+
+Wall time of this file alone on one MI355X: 8.80 s for its 202 tests (7.1 s of it in the audits, 702 launches; the 24 training cases together
+1.8 s, each below 0.2 s: none is among the file's eight slowest tests); the parent commit's file on the same box, same visit: 6.99 s for 178 tests
+(522 launches); the whole GPU suite then: 234.04 s for 597 tests (EXPERIMENTS.md, "Training edge audit")."""
 import time
 
 import pytest
