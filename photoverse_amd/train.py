@@ -124,7 +124,8 @@ from typing import Dict, List  # noqa: E402
 from . import ops as _ops  # noqa: E402
 from .lora import LoRALinear  # noqa: E402
 from .tape import Tape, Var, conv3_dgrad_weight  # noqa: E402
-from .unet import ResnetBlock2D, Transformer2DModel, _conv1_w, _conv3_w, _f16, _f32  # noqa: E402
+from .unet import (ResnetBlock2D, Transformer2DModel, _conv1_w, _conv3_w, _f16, _f32, conv_in_weight, conv_out_weight,  # noqa: E402
+                   time_projection, unet_stages)
 
 
 class TrainStep:
@@ -395,53 +396,37 @@ class TrainStep:
             te = rf.timestep_embedding(self.timesteps, None, B, c0)
         e1 = rf.gemm(te, _f16(u.time_embedding.linear_1.weight), bias=_f32(u.time_embedding.linear_1.bias), act=_ops.ACT_SILU)
         e2 = rf.gemm(e1, _f16(u.time_embedding.linear_2.weight), bias=_f32(u.time_embedding.linear_2.bias), act=_ops.ACT_SILU)
-        resnets = [m for m in u.modules() if isinstance(m, ResnetBlock2D)]
-        toffs, off = {}, 0
-        for m in resnets:
-            toffs[id(m)] = off
-            off += m.conv1.out_channels
-        pad = (-off) % 160
-        wt = torch.cat([_f16(m.time_emb_proj.weight) for m in resnets] +
-                       ([torch.zeros(pad, resnets[0].time_emb_proj.in_features, dtype=torch.float16, device=dev)] if pad else []), 0)
-        bt = torch.cat([_f32(m.time_emb_proj.bias) for m in resnets] + ([torch.zeros(pad, device=dev)] if pad else []), 0)
-        temb_all = rf.gemm(e2, wt.contiguous(), bias=bt.contiguous(), out_f32=True)
-        kin = cfg.in_channels * 9
-        kpad = (kin + 63) // 64 * 64
-        cols = rf.im2col3x3(noisy, batch=B, cin=cfg.in_channels, h=h, wd=w, kpad=kpad)
-        w_in = torch.zeros(c0, kpad, dtype=torch.float16, device=dev)
-        w_in[:, :kin] = u.conv_in.weight.detach().reshape(c0, kin).to(torch.float16)
-        x = Var(rf.gemm(cols, w_in, bias=_f32(u.conv_in.bias), rows_per_image=h * w, colstats=True), False)
-        skips = [(x, h, w)]
-        for bi, blk in enumerate(u.down_blocks):
-            for i, res in enumerate(blk.resnets):
-                x = self._resnet(res, x, None, h, w, temb_all, toffs[id(res)])
-                if blk.has_attn:
-                    x = self._transformer(f"down_blocks.{bi}.attentions.{i}", blk.attentions[i], x, h, w, text, ip_rows)
-                skips.append((x, h, w))
-            if blk.downsamplers is not None:
-                conv = blk.downsamplers[0].conv
-                x = tp.conv3(x, _conv3_w(conv.weight), conv3_dgrad_weight(conv.weight), bias=_f32(conv.bias), batch=B, h=h, w=w, stride=2)
+        stages = unet_stages(u)
+        wt, bt = time_projection(stages)
+        temb_all = rf.gemm(e2, wt, bias=bt, out_f32=True)
+        x, skips = None, []
+        for st in stages:                                   # the walk UNetEngine._build records ranges of
+            m = st.module
+            if st.kind == "conv_in":
+                w_in = conv_in_weight(u)
+                cols = rf.im2col3x3(noisy, batch=B, cin=cfg.in_channels, h=h, wd=w, kpad=w_in.shape[1])
+                x = Var(rf.gemm(cols, w_in, bias=_f32(m.bias), rows_per_image=h * w, colstats=True), False)
+            elif st.kind == "resnet":
+                sk = None
+                if st.skip < 0:
+                    sk, sh, sw = skips.pop()
+                    assert (sh, sw) == (h, w)
+                x = self._resnet(m, x, sk, h, w, temb_all, st.toff)
+            elif st.kind == "transformer":
+                x = self._transformer(st.name, m, x, h, w, text, ip_rows)
+            elif st.kind == "downsample":
+                x = tp.conv3(x, _conv3_w(m.conv.weight), conv3_dgrad_weight(m.conv.weight), bias=_f32(m.conv.bias), batch=B, h=h, w=w, stride=2)
                 h, w = h // 2, w // 2
-                skips.append((x, h, w))
-        mb = u.mid_block
-        x = self._resnet(mb.resnets[0], x, None, h, w, temb_all, toffs[id(mb.resnets[0])])
-        x = self._transformer("mid_block.attentions.0", mb.attentions[0], x, h, w, text, ip_rows)
-        x = self._resnet(mb.resnets[1], x, None, h, w, temb_all, toffs[id(mb.resnets[1])])
-        for bi, blk in enumerate(u.up_blocks):
-            for i, res in enumerate(blk.resnets):
-                sk, sh, sw = skips.pop()
-                assert (sh, sw) == (h, w)
-                x = self._resnet(res, x, sk, h, w, temb_all, toffs[id(res)])
-                if blk.has_attn:
-                    x = self._transformer(f"up_blocks.{bi}.attentions.{i}", blk.attentions[i], x, h, w, text, ip_rows)
-            if blk.upsamplers is not None:
-                conv = blk.upsamplers[0].conv
-                x = tp.conv3(x, _conv3_w(conv.weight), conv3_dgrad_weight(conv.weight), bias=_f32(conv.bias), batch=B, h=h, w=w, upsample=1)
+            elif st.kind == "upsample":
+                x = tp.conv3(x, _conv3_w(m.conv.weight), conv3_dgrad_weight(m.conv.weight), bias=_f32(m.conv.bias), batch=B, h=h, w=w, upsample=1)
                 h, w = h * 2, w * 2
-        xn = tp.groupnorm(x, _f32(u.conv_norm_out.weight), _f32(u.conv_norm_out.bias), batch=B, hw=h * w, eps=u.conv_norm_out.eps, act=_ops.ACT_SILU)
-        wo = u.conv_out.weight.detach().permute(0, 2, 3, 1).reshape(cfg.out_channels, -1).to(torch.float16).contiguous()
-        noise_pred = rf.conv_out(xn.t, wo, _f32(u.conv_out.bias), batch=B, cin=c0, h=h, wd=w, cout=cfg.out_channels)
-
+            else:
+                xn = tp.groupnorm(x, _f32(u.conv_norm_out.weight), _f32(u.conv_norm_out.bias), batch=B, hw=h * w, eps=u.conv_norm_out.eps,
+                                  act=_ops.ACT_SILU)
+                noise_pred = rf.conv_out(xn.t, conv_out_weight(u), _f32(m.bias), batch=B, cin=c0, h=h, wd=w, cout=cfg.out_channels)
+            if st.skip > 0:
+                skips.append((x, h, w))
+        assert not skips
 
         def seed(dpred):
             oc = cfg.out_channels

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import os
 from types import SimpleNamespace
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -188,12 +188,110 @@ def _conv1_w(w: torch.Tensor) -> torch.Tensor:
     return w.detach().reshape(w.shape[0], -1).to(torch.float16).contiguous()
 
 
+class Stage(NamedTuple):
+    """One launch group of a UNet forward (``unet_stages``)."""
+    kind: str                 # "conv_in" | "resnet" | "transformer" | "downsample" | "upsample" | "conv_out"
+    module: nn.Module
+    name: str                 # the module's path in the UNet: what the plans call it (``vnorms``, ``perturb``, ``trunk_points``)
+    block: Tuple[str, int]    # ("down", bi) | ("mid", 0) | ("up", bi); conv_in / conv_out belong to the first down / last up block
+    level: int                # its input is (H >> level) x (W >> level)
+    skip: int                 # +1: its output is pushed as a skip connection; -1: it pops one (the second input of an up-path resnet); 0
+    toff: int = 0             # a resnet's columns in the stacked time-embedding projection (``time_projection``): toff .. toff + tcols
+    tcols: int = 0
+
+
+def unet_stages(unet) -> Tuple[Stage, ...]:
+    """The forward of ``unet`` as the sequence of its launch groups, in execution order: THE walk both the inference plans (``UNetEngine._build``) and
+    the training tape (``train.TrainStep._unet_pass``) record.  Host-side: reads the module tree only (a CPU or ``meta`` model will do)."""
+    out, off = [], 0
+
+    def add(kind, m, name, block, level, skip=0):
+        nonlocal off
+        cols = m.conv1.out_channels if kind == "resnet" else 0
+        out.append(Stage(kind, m, name, block, level, skip, off if cols else 0, cols))
+        off += cols
+
+    add("conv_in", unet.conv_in, "conv_in", ("down", 0), 0, +1)
+    lvl = 0
+    for bi, blk in enumerate(unet.down_blocks):
+        for i, res in enumerate(blk.resnets):
+            add("resnet", res, f"down_blocks.{bi}.resnets.{i}", ("down", bi), lvl, 0 if blk.has_attn else +1)
+            if blk.has_attn:
+                add("transformer", blk.attentions[i], f"down_blocks.{bi}.attentions.{i}", ("down", bi), lvl, +1)
+        if blk.downsamplers is not None:
+            add("downsample", blk.downsamplers[0], f"down_blocks.{bi}.downsamplers.0", ("down", bi), lvl, +1)
+            lvl += 1
+    mb = unet.mid_block
+    add("resnet", mb.resnets[0], "mid_block.resnets.0", ("mid", 0), lvl)
+    add("transformer", mb.attentions[0], "mid_block.attentions.0", ("mid", 0), lvl)
+    add("resnet", mb.resnets[1], "mid_block.resnets.1", ("mid", 0), lvl)
+    for bi, blk in enumerate(unet.up_blocks):
+        for i, res in enumerate(blk.resnets):
+            add("resnet", res, f"up_blocks.{bi}.resnets.{i}", ("up", bi), lvl, -1)
+            if blk.has_attn:
+                add("transformer", blk.attentions[i], f"up_blocks.{bi}.attentions.{i}", ("up", bi), lvl)
+        if blk.upsamplers is not None:
+            add("upsample", blk.upsamplers[0], f"up_blocks.{bi}.upsamplers.0", ("up", bi), lvl)
+            lvl -= 1
+    add("conv_out", unet.conv_out, "conv_out", ("up", len(unet.up_blocks) - 1), lvl)
+    return tuple(out)
+
+
+def time_projection_width(stages) -> int:
+    """Columns of the stacked time-embedding projection: every resnet's ``conv1.out_channels``, padded to whole 160-column GEMM tiles."""
+    n = sum(st.tcols for st in stages)
+    return n + (-n) % 160
+
+
+def time_projection(stages) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Every ``time_emb_proj`` as ONE Linear: (fp16 weight [``time_projection_width``, temb], fp32 bias), resnet ``st`` owning rows
+    ``st.toff .. st.toff + st.tcols``; the padding rows are zero."""
+    lins = [st.module.time_emb_proj for st in stages if st.kind == "resnet"]
+    dev = lins[0].weight.device
+    pad = time_projection_width(stages) - sum(lin.out_features for lin in lins)
+    wt = torch.cat([_f16(lin.weight) for lin in lins] + ([torch.zeros(pad, lins[0].in_features, dtype=torch.float16, device=dev)] if pad else []), 0)
+    bt = torch.cat([_f32(lin.bias) for lin in lins] + ([torch.zeros(pad, device=dev)] if pad else []), 0)
+    return wt.contiguous(), bt.contiguous()
+
+
+def conv_in_weight(unet) -> torch.Tensor:
+    """conv_in (cin = 4) runs as im2col + MFMA GEMM: fp16 [c0, kpad], K = 9 * cin zero-padded to a multiple of 64 (``kpad`` = its width)."""
+    wgt = unet.conv_in.weight.detach()
+    c0, kin = wgt.shape[0], wgt.shape[1] * 9
+    w_in = torch.zeros(c0, (kin + 63) // 64 * 64, dtype=torch.float16, device=wgt.device)
+    w_in[:, :kin] = wgt.reshape(c0, kin).to(torch.float16)
+    return w_in
+
+
+def conv_out_weight(unet) -> torch.Tensor:
+    """conv_out's weight for ``Recorder.conv_out``: fp16 [cout, 3 * 3 * c0], tap-major."""
+    return _conv3_w(unet.conv_out.weight)
+
+
+def plan_ranges(stages, segment: Optional[str] = None, split: int = 2, prefix: bool = False, trunk_at: Optional[str] = None) -> Tuple[tuple, ...]:
+    """What a ``UNetEngine`` records, as ranges ``(first, last, adopts, writes)`` of ``stages`` (indices, ``last`` inclusive).  ``adopts``: the tensors
+    of another plan the range starts from - None (the latents), ``"prefix"``, ``"mid_in"``, ``"mid_out"`` or ``"trunk"``; ``writes``: where its last
+    launch writes - None (a buffer of its own), ``"prefix_out"``, ``"mid_in"`` or ``"mid_out"``.  ``prefix``: the plan is given another plan's
+    prefix; ``trunk_at``: the transformer a perturbed plan on a shared trunk starts at.  One range per recorder: ``"outer"`` has two.  Host-side."""
+    n = len(stages)
+    start = (2, "prefix") if prefix else (0, None)     # a prefix-fed plan resumes inside stage 2, the first transformer, behind its attn1
+    if trunk_at is not None:
+        return ((next(i for i, st in enumerate(stages) if st.name == trunk_at), n - 1, "trunk", None),)
+    if segment == "prefix":
+        return ((0, 2, None, "prefix_out"),)
+    if segment is None:
+        return ((start[0], n - 1, start[1], None),)
+    n_up = stages[-1].block[1] + 1
+    d = next(i for i, st in enumerate(stages) if st.kind == "downsample" and st.block == ("down", split - 1))     # writes the merged part's input
+    u = next(i for i, st in enumerate(stages) if st.kind == "upsample" and st.block == ("up", n_up - split - 1))  # writes the merged part's output
+    if segment == "mid":
+        return ((d + 1, u, "mid_in", "mid_out"),)
+    return ((start[0], d, start[1], "mid_in"), (u + 1, n - 1, "mid_out", None))
+
+
 def transformer_names(unet) -> Tuple[str, ...]:
     """The transformers of ``unet`` under the names ``UNetEngine._transformer`` receives, in execution order (down path, mid block, up path)."""
-    names = [f"down_blocks.{bi}.attentions.{i}" for bi, blk in enumerate(unet.down_blocks) if blk.has_attn for i in range(len(blk.attentions))]
-    names += [f"mid_block.attentions.{i}" for i in range(len(unet.mid_block.attentions))]
-    names += [f"up_blocks.{bi}.attentions.{i}" for bi, blk in enumerate(unet.up_blocks) if blk.has_attn for i in range(len(blk.attentions))]
-    return tuple(names)
+    return tuple(st.name for st in unet_stages(unet) if st.kind == "transformer")
 
 
 def resolve_pag_layers(unet, layers=("mid_block",)) -> Tuple[str, ...]:
@@ -249,7 +347,17 @@ def fold_identity_attention(attn: Attention) -> Tuple[torch.Tensor, torch.Tensor
 
 
 class UNetEngine:
-    """Static launch plan of one UNet forward for a fixed (batch, height, width, ip tokens, timestep rows)."""
+    """Static launch plan of one UNet forward for a fixed (batch, height, width, ip tokens, timestep rows).
+
+    Every plan kind is a range of the one stage list ``unet_stages(unet)``, starting from tensors somebody else wrote (``plan_ranges``: first stage, last
+    stage, what the range adopts at entry, where its last launch writes); ``_build`` records exactly that range, after a time embedding of its own:
+
+    - whole plan: all stages, from the latents to ``out``;
+    - ``segment="prefix"``: conv_in, the first resnet and the first transformer up to its attn1 -> ``prefix_out``;
+    - ``prefix=``: adopts those three tensors and resumes inside the first transformer, behind attn1;
+    - ``segment="outer"``: two ranges - the head into ``rec_head``, ending on the downsample that writes ``mid_in``; the tail into ``rec_tail``, adopting ``mid_out``;
+    - ``segment="mid"``: the stages between those two at batch 2B, adopting ``mid_in``; its last launch, an upsample, writes ``mid_out``;
+    - ``trunk=``: from the first perturbed transformer on, adopting ``trunk.trunk_points[name]`` (activation and skip stack)."""
 
     def __init__(self, unet: "UNet2DConditionModel", batch: int, h: int, w: int, n_ip: int, t_rows: int, device,
                  timesteps: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None, n_text: int = 77,
@@ -504,27 +612,25 @@ class UNetEngine:
     def _build(self):
         u, rec, B = self.unet, self.rec, self.B
         cfg = u.config
-        h, w = self.H, self.W
         c0 = cfg.block_out_channels[0]
-        # time embedding: sinusoid -> linear_1+SiLU -> linear_2 (+SiLU, the only consumer is time_emb_proj(silu(emb)))
+        stages = unet_stages(u)
+        # time embedding: sinusoid -> linear_1+SiLU -> linear_2 (+SiLU, the only consumer is time_emb_proj(silu(emb))); every plan kind records its own
         te = rec.timestep_embedding(self.timesteps, self.state, self.t_rows, c0)
         e1 = rec.gemm(te, _f16(u.time_embedding.linear_1.weight), bias=_f32(u.time_embedding.linear_1.bias), act=ACT_SILU)
         e2 = rec.gemm(e1, _f16(u.time_embedding.linear_2.weight), bias=_f32(u.time_embedding.linear_2.bias), act=ACT_SILU)
-        resnets = [m for m in u.modules() if isinstance(m, ResnetBlock2D)]
-        toffs, off = {}, 0
-        for m in resnets:
-            toffs[id(m)] = off
-            off += m.conv1.out_channels
-        pad = (-off) % 160
-        wt = torch.cat([_f16(m.time_emb_proj.weight) for m in resnets] +
-                       ([torch.zeros(pad, resnets[0].time_emb_proj.in_features, dtype=torch.float16, device=rec.device)] if pad else []), 0)
-        bt = torch.cat([_f32(m.time_emb_proj.bias) for m in resnets] + ([torch.zeros(pad, device=rec.device)] if pad else []), 0)
-        temb_all = rec.gemm(e2, wt.contiguous(), bias=bt.contiguous(), out_f32=True)
+        wt, bt = time_projection(stages)
+        temb_all = rec.gemm(e2, wt, bias=bt, out_f32=True)
 
-        seg, split = self.segment, self.split
-        n_lv = len(u.down_blocks)
-        if seg in ("outer", "mid") and not (0 < split < n_lv):
+        seg, split, pre = self.segment, self.split, self.prefix_in
+        if seg in ("outer", "mid") and not (0 < split < len(u.down_blocks)):
             raise ValueError("split must leave at least one resolution level on either side")
+        names = [st.name for st in stages if st.kind == "transformer"]
+        unknown = [nm for nm in self.perturb if nm not in names]
+        if unknown:
+            raise ValueError(f"perturb names no transformer of this UNet: {unknown}")
+        first = u.down_blocks[0]
+        if (seg == "prefix" or pre is not None) and not (first.has_attn and len(first.resnets) >= 1):
+            raise ValueError("the shared prefix needs an attention down block first (conv_in -> ResnetBlock -> transformer block)")
 
         def adopt(t_cs, rows):
             """a tensor written by ANOTHER plan (with its column statistics) becomes this plan's current activation"""
@@ -540,123 +646,72 @@ class UNetEngine:
                 self.rec.colstats.pop(key, None)
             return t
 
-        # perturbed plan on a shared trunk: nothing is recorded (x is None, the skips are placeholders) until the first perturbed transformer, in
-        # execution order, whose entry state is adopted from the conditional plan
-        skipping = self.trunk is not None
-        trunk_at = next((nm for nm in transformer_names(u) if nm in self.perturb), None)
-        unknown = [nm for nm in self.perturb if nm not in transformer_names(u)]
-        if unknown:
-            raise ValueError(f"perturb names no transformer of this UNet: {unknown}")
-
         def cs_of(t):
             return self.rec.colstats.get((t.data_ptr(), t.shape[0], t.shape[1]))
 
-        def xf(name, m, x, h, w, **kw):
-            nonlocal skipping
-            if skipping and name == trunk_at:
-                tx, tskips = self.trunk.trunk_points[name]
-                assert [(sh, sw) for _, _, sh, sw in tskips] == [(sh, sw) for _, sh, sw in skips]
+        # a perturbed plan on a shared trunk starts at its first perturbed transformer, in execution order, from the conditional plan's tensors there
+        trunk_at = next(nm for nm in names if nm in self.perturb) if self.trunk is not None else None
+        skips = []
+        for (i0, i1, adopts, writes), rec in zip(plan_ranges(stages, seg, split, pre is not None, trunk_at),
+                                                 (self.rec_head, self.rec_tail) if seg == "outer" else (rec,)):
+            self.rec = rec                                            # what the block recorders record into
+            h, w = self.H >> stages[i0].level, self.W >> stages[i0].level
+            x = resume_hs = None
+            if adopts == "prefix":
+                # conv_in, the first ResnetBlock and the first transformer block up to attn1 were recorded by the prefix plan
+                skips.append((adopt(pre["conv_in"], B * h * w), h, w))
+                x, resume_hs = adopt(pre["res"], B * h * w), pre["hs"]
+            elif adopts == "trunk":
+                tx, tskips = self.trunk.trunk_points[trunk_at]
+                assert len(tskips) == sum(st.skip for st in stages[:i0])
                 x = adopt(tx, B * h * w)
                 skips[:] = [(adopt((t, cs), B * sh * sw), sh, sw) for t, cs, sh, sw in tskips]
-                skipping = False
-            elif seg is None and not self.perturb:
-                self.trunk_points[name] = ((x, cs_of(x)), [(t, cs_of(t), sh, sw) for t, sh, sw in skips])
-            if skipping:
-                return None
-            return self._transformer(name, m, x, B, h, w, **kw)
-
-        pre = self.prefix_in
-        first = u.down_blocks[0]
-        if (seg == "prefix" or pre is not None) and not (first.has_attn and len(first.resnets) >= 1):
-            raise ValueError("the shared prefix needs an attention down block first (conv_in -> ResnetBlock -> transformer block)")
-        if skipping:
-            x, skips = None, [(None, h, w)]
-        elif pre is not None:
-            # conv_in, the first ResnetBlock and the first transformer block up to attn1 were recorded by the prefix plan
-            x = adopt(pre["conv_in"], B * h * w)
-            skips = [(x, h, w)]
-        elif seg != "mid":
-            # conv_in (cin = 4): im2col to K = 36 -> 64 (zero padded), then the MFMA GEMM
-            kin = cfg.in_channels * 9
-            kpad = (kin + 63) // 64 * 64
-            cols = rec.im2col3x3(self.x_in, batch=B, cin=cfg.in_channels, h=h, wd=w, kpad=kpad)
-            w_in = torch.zeros(c0, kpad, dtype=torch.float16, device=rec.device)
-            w_in[:, :kin] = u.conv_in.weight.detach().reshape(c0, kin).to(torch.float16)
-            x = rec.gemm(cols, w_in, bias=_f32(u.conv_in.bias), rows_per_image=h * w, colstats=True)
-            skips = [(x, h, w)]
-            if seg == "prefix":
-                key = lambda t: (t.data_ptr(), t.shape[0], t.shape[1])
-                res0 = first.resnets[0]
-                xr = self._resnet(res0, x, None, B, h, w, temb_all, toffs[id(res0)])
-                hs = self._transformer("down_blocks.0.attentions.0", first.attentions[0], xr, B, h, w, stop_after_attn1=True)
-                self.prefix_out = {"conv_in": (x, rec.colstats.get(key(x))), "res": (xr, rec.colstats.get(key(xr))), "hs": hs}
-                self.out = hs
-                return
-        else:
-            h, w = h >> split, w >> split
-            x = adopt(self.mid_in, B * h * w)
-            skips = [(x, h, w)]
-        for bi, blk in enumerate(u.down_blocks):
-            if (seg == "outer" and bi >= split) or (seg == "mid" and bi < split):
-                continue
-            for i, res in enumerate(blk.resnets):
-                if pre is not None and bi == 0 and i == 0:
-                    x = adopt(pre["res"], B * h * w)
-                    x = xf("down_blocks.0.attentions.0", blk.attentions[0], x, h, w, resume_hs=pre["hs"])
+            elif adopts is not None:
+                # a seam of the low-resolution merge: this branch's half (the merged plan: the whole) of the buffer the plan before wrote
+                x = adopt(getattr(self, adopts), B * h * w)
+                if stages[i0 - 1].skip > 0:
+                    skips.append((x, h, w))                           # (the skip of the downsample at the seam belongs to the merged part)
+            for st in stages[i0:i1 + 1]:
+                m = st.module
+                ends = st is stages[i1] and writes is not None        # this launch group's output belongs to another plan
+                if st.kind == "conv_in":
+                    # conv_in (cin = 4): im2col to K = 36 -> 64 (zero padded), then the MFMA GEMM
+                    w_in = conv_in_weight(u)
+                    cols = rec.im2col3x3(self.x_in, batch=B, cin=cfg.in_channels, h=h, wd=w, kpad=w_in.shape[1])
+                    x = rec.gemm(cols, w_in, bias=_f32(m.bias), rows_per_image=h * w, colstats=True)
+                elif st.kind == "resnet":
+                    sk = None
+                    if st.skip < 0:
+                        sk, sh, sw = skips.pop()
+                        assert (sh, sw) == (h, w)
+                        if self.freeu is not None and st.block[1] < 2:
+                            x, sk = rec.freeu(x, sk, batch=B, h=h, w=w, b=self.freeu[st.block[1]], s=self.freeu[2 + st.block[1]])
+                    x = self._resnet(m, x, sk, B, h, w, temb_all, st.toff)   # channel concat [x | skip] is never materialised
+                elif st.kind == "transformer":
+                    if seg is None and not self.perturb:
+                        self.trunk_points[st.name] = ((x, cs_of(x)), [(t, cs_of(t), sh, sw) for t, sh, sw in skips])
+                    if writes == "prefix_out":
+                        hs = self._transformer(st.name, m, x, B, h, w, stop_after_attn1=True)
+                        x0 = skips[0][0]
+                        self.prefix_out = {"conv_in": (x0, cs_of(x0)), "res": (x, cs_of(x)), "hs": hs}
+                        x = hs
+                    else:
+                        x, resume_hs = self._transformer(st.name, m, x, B, h, w, resume_hs=resume_hs), None
+                elif st.kind in ("downsample", "upsample"):
+                    # at a seam: this branch's half of the merged part's input / the merged part's output, with its column statistics
+                    out, out_cs = getattr(self, writes) if ends else (None, None)
+                    geo = dict(hout=h // 2, wout=w // 2, stride=2) if st.kind == "downsample" else dict(hout=h * 2, wout=w * 2, upsample=1)
+                    x = rec.gemm(x, _conv3_w(m.conv.weight), bias=_f32(m.conv.bias), conv=dict(batch=B, hin=h, win=w, **geo), colstats=True,
+                                 out=out, colstats_out=out_cs)
+                    h, w = geo["hout"], geo["wout"]
+                else:
+                    xn = rec.groupnorm(x, _f32(u.conv_norm_out.weight), _f32(u.conv_norm_out.bias), batch=B, hw=h * w,
+                                       eps=u.conv_norm_out.eps, act=ACT_SILU)
+                    x = rec.conv_out(xn, conv_out_weight(u), _f32(m.bias), batch=B, cin=c0, h=h, wd=w, cout=cfg.out_channels, out=self.out_buf)
+                if st.skip > 0 and not ends:
                     skips.append((x, h, w))
-                    continue
-                x = None if skipping else self._resnet(res, x, None, B, h, w, temb_all, toffs[id(res)])
-                if blk.has_attn:
-                    x = xf(f"down_blocks.{bi}.attentions.{i}", blk.attentions[i], x, h, w)
-                skips.append((x, h, w))
-            if blk.downsamplers is not None:
-                conv = blk.downsamplers[0].conv
-                boundary = seg == "outer" and bi == split - 1         # this branch's half of the merged part's input
-                if not skipping:
-                    x = rec.gemm(x, _conv3_w(conv.weight), bias=_f32(conv.bias),
-                                 conv=dict(batch=B, hin=h, win=w, hout=h // 2, wout=w // 2, stride=2), colstats=True,
-                                 out=self.mid_in[0] if boundary else None, colstats_out=self.mid_in[1] if boundary else None)
-                h, w = h // 2, w // 2
-                if not boundary:
-                    skips.append((x, h, w))                           # (at the boundary the skip belongs to the merged part)
-        if seg != "outer":
-            mb = u.mid_block
-            x = None if skipping else self._resnet(mb.resnets[0], x, None, B, h, w, temb_all, toffs[id(mb.resnets[0])])
-            x = xf("mid_block.attentions.0", mb.attentions[0], x, h, w)
-            x = None if skipping else self._resnet(mb.resnets[1], x, None, B, h, w, temb_all, toffs[id(mb.resnets[1])])
-        n_up = len(u.up_blocks)
-        for bi, blk in enumerate(u.up_blocks):
-            outer_up = bi >= n_up - split
-            if (seg == "outer" and not outer_up) or (seg == "mid" and outer_up):
-                continue
-            if seg == "outer" and bi == n_up - split:
-                rec = self.rec = self.rec_tail                        # the tail plan starts from this branch's half of the merged output
-                h, w = self.H >> (split - 1), self.W >> (split - 1)
-                x = adopt(self.mid_out, B * h * w)
-            for i, res in enumerate(blk.resnets):
-                sk, sh, sw = skips.pop()
-                assert (sh, sw) == (h, w)
-                if self.freeu is not None and bi < 2 and not skipping:
-                    x, sk = rec.freeu(x, sk, batch=B, h=h, w=w, b=self.freeu[bi], s=self.freeu[2 + bi])
-                x = None if skipping else self._resnet(res, x, sk, B, h, w, temb_all, toffs[id(res)])   # channel concat [x | skip] is never materialised
-                if blk.has_attn:
-                    x = xf(f"up_blocks.{bi}.attentions.{i}", blk.attentions[i], x, h, w)
-            if blk.upsamplers is not None:
-                conv = blk.upsamplers[0].conv
-                boundary = seg == "mid" and bi == n_up - split - 1
-                if not skipping:
-                    x = rec.gemm(x, _conv3_w(conv.weight), bias=_f32(conv.bias),
-                                 conv=dict(batch=B, hin=h, win=w, hout=h * 2, wout=w * 2, upsample=1), colstats=True,
-                                 out=self.mid_out[0] if boundary else None, colstats_out=self.mid_out[1] if boundary else None)
-                h, w = h * 2, w * 2
-        assert not skipping and not skips, "every skip connection is consumed inside the plan segment that produced it"
-        if seg == "mid":
-            self.out = x
-            return
-        xn = rec.groupnorm(x, _f32(u.conv_norm_out.weight), _f32(u.conv_norm_out.bias), batch=B, hw=h * w,
-                           eps=u.conv_norm_out.eps, act=ACT_SILU)
-        wo = u.conv_out.weight.detach().permute(0, 2, 3, 1).reshape(cfg.out_channels, -1).to(torch.float16).contiguous()
-        self.out = rec.conv_out(xn, wo, _f32(u.conv_out.bias), batch=B, cin=c0, h=h, wd=w, cout=cfg.out_channels, out=self.out_buf)
+        assert seg == "prefix" or not skips, "every skip connection is consumed inside the plan segment that produced it"
+        self.out = x
         if seg == "outer":
             self.rec = Recorder.concat(self.rec_head, self.rec_tail)      # introspection / timing view of the branch's own launches
 

@@ -5,6 +5,9 @@ seeded run; ``main`` writes them for ``CASES`` to ``tests/golden/plan_signatures
 launch list or the bits - from a checkout of the commit that is to be the reference, never from the code under test:
 
     python tools/plan_signatures.py [--commit HASH] [--out FILE] [case ...]
+
+``--train``: the same for the training plans - every recorder of the ``TrainStep``s in ``TRAIN_CASES``, their dropout sites and fusion names, the sha256 of
+loss and gradients after an eager and after a replayed step - to ``tests/golden/train_plan_signatures.json`` (``tests/test_train_plan_signatures_gpu.py``).
 """
 import argparse
 import hashlib
@@ -150,21 +153,124 @@ def unpack(doc: dict) -> dict:
     return cases
 
 
+# ---------------------------------------------------------------------------------------------------------------- the training plans
+TRAIN_GOLDEN = os.path.join(ROOT, "tests", "golden", "train_plan_signatures.json")
+_TRAIN_TINY = dict(unet="tiny", B=2, S=16, E=3, lora_dropout=0.0, face=True, run=True)      # tests' test_training_step_is_bit_reproducible
+#: name -> a ``TrainStep``: LoRA r = 4 with ``lora_dropout`` (None: no LoRA), the face-loss branch, and whether two seeded steps run (eager, then replayed)
+TRAIN_CASES = {
+    "train-tiny-lora-face": dict(_TRAIN_TINY),
+    "train-tiny-lora-dropout-face": dict(_TRAIN_TINY, lora_dropout=0.1),       # the un-merged low-rank branches and their dropout sites
+    "train-tiny-plain": dict(_TRAIN_TINY, E=1, lora_dropout=None, face=False),
+    "train-full-built": dict(unet="full", B=1, S=32, E=1, lora_dropout=None, face=False, run=False),   # launch lists of the four-level walk
+}
+_VIS = dict(hidden_size=256, num_attention_heads=4, intermediate_size=512, num_hidden_layers=3, image_size=56, patch_size=14)
+_TXT = dict(vocab_size=49408, hidden_size=768, num_attention_heads=12, intermediate_size=512, num_hidden_layers=2, max_position_embeddings=77)
+_VAE = dict(block_out_channels=(128, 128, 256, 256), layers_per_block=1)
+
+
+def _sha(tensors) -> str:
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().float().contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
+def train_recorders(step) -> dict:
+    """Every recorder of a ``TrainStep`` by name: the main tape's two plans and, with the face loss, that branch's five."""
+    recs = dict(rf=step.tape.rf, rb=step.tape.rb)
+    if step.face is not None:
+        f = step.face
+        recs.update(face_rec_cond=f.rec_cond, face_loop_rf=f.loop_tape.rf, face_rec_stack=f.rec_stack, face_rec_last=f.rec_last, face_rb=f.tape.rb)
+    return recs
+
+
+def run_train_case(name: str, full=None) -> dict:
+    """Build ``TRAIN_CASES[name]`` on seeded models (``full``: the SD-v1.5-sized UNet on the GPU for the case that wants one) and return its signature:
+    every recorder's launch list, ``dropout_sites``, ``fusion_names`` and - where the case runs - the sha256 of (loss, face loss, every trainable
+    gradient) after the first, eager step and after the second, replayed one on the same inputs."""
+    from oracle.unet_ref import TINY_CONFIG
+    from photoverse_amd.lora import LoraConfig
+    from photoverse_amd.loss import FaceLoss
+    from photoverse_amd.modeling_utils import load_models
+    from photoverse_amd.train import TrainStep
+    c = TRAIN_CASES[name]
+    B, S, E, lora = c["B"], c["S"], c["E"], c["lora_dropout"] is not None
+    _, text_encoder, vae, unet, _, image_adapter, text_adapter, scheduler, _ = load_models(
+        None, E - 1, use_lora=lora, lora_config=LoraConfig(r=4, lora_alpha=4, lora_dropout=c["lora_dropout"]) if lora else None,
+        unet_config=TINY_CONFIG, vision_config=_VIS, text_config=_TXT, vae_config=_VAE, seed=91)
+    if c["unet"] == "full":
+        unet = full
+    for m in (unet, text_encoder, image_adapter, text_adapter, vae):
+        m.to("cuda")
+    torch.manual_seed(93)
+    face = dict(face_loss=FaceLoss("cuda", "arcface"), vae=vae, face_samples=1, infer_steps=3, image_size=8 * S) if c["face"] else {}
+    step = TrainStep(unet, text_encoder, text_adapter, image_adapter, batch=B, h=S, w=S, n_tokens=E, clip_tokens=17, clip_dim=256, grad_scale=512.0,
+                     noise_scheduler=scheduler, **face)
+    sig = dict(recorders={k: _launches(r) for k, r in train_recorders(step).items()}, dropout_sites=step.dropout_sites,
+               fusion_names=step.fusion_names, sha256=[])
+    if c["run"]:
+        g = torch.Generator().manual_seed(92)
+        fi = None
+        if c["face"]:
+            fi = dict(pixel_values=(torch.rand(1, 3, 8 * S, 8 * S, generator=g) * 2 - 1).cuda(), start_latents=torch.randn(1, 4, S, S, generator=g).cuda(),
+                      image_embeddings=torch.randn(1, 17, 256, generator=g).half().cuda(),
+                      uncond_image_embeddings=torch.randn(1, 17, 256, generator=g).half().cuda(),
+                      text_input_ids=torch.randint(0, 1000, (1, 77), generator=g).cuda(), placeholder_idx=torch.tensor([[4]]).cuda(),
+                      uncond_input_ids=torch.randint(0, 1000, (1, 77), generator=g).cuda(), forced_fusion=([0.5, 0.1, 0.9, 0.5], [0.9, 0.5, 0.5, 0.1]))
+        kw = dict(noisy_latents=torch.randn(B, 4, S, S, generator=g).cuda(), noise=torch.randn(B, 4, S, S, generator=g).cuda(),
+                  timesteps=torch.tensor([5, 900][:B]), text_input_ids=torch.randint(0, 1000, (B, 77), generator=g).cuda(),
+                  placeholder_idx=torch.tensor([[2], [9]][:B]).cuda(), image_embeddings=[torch.randn(B, 17, 256, generator=g).half().cuda() for _ in range(E)],
+                  forced_fusion=[0.1, 0.5, 0.9, 0.5], face_inputs=fi)
+        params = [p for ps in step.trainable_parameters().values() for p in ps]
+        for _ in range(2):                                  # the first step runs the plans eagerly, the second captures and replays them
+            out = step.step(**kw)
+            torch.cuda.synchronize()
+            sig["sha256"].append(_sha([out["loss"]] + ([out["face_loss"]] if c["face"] else []) + [p.grad for p in params]))
+        assert step.graph is not None and (step.face is None or step.face.graph is not None)
+    return json.loads(json.dumps(sig))
+
+
+def pack_train(sigs: dict, commit: str) -> dict:
+    """``pack`` for the training signatures: one launch table, the recorders as index lists."""
+    table = {}
+    cases = json.loads(json.dumps(sigs))
+    for sig in cases.values():
+        sig["recorders"] = {k: [table.setdefault(json.dumps(launch), len(table)) for launch in v] for k, v in sig["recorders"].items()}
+    return dict(commit=commit, launches=[json.loads(s) for s in table], cases=cases)
+
+
+def unpack_train(doc: dict) -> dict:
+    cases = json.loads(json.dumps(doc["cases"]))
+    for sig in cases.values():
+        sig["recorders"] = {k: [doc["launches"][i] for i in v] for k, v in sig["recorders"].items()}
+    return cases
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("cases", nargs="*", help="default: all")
     ap.add_argument("--commit", help="the commit this checkout is at (default: git rev-parse HEAD)")
-    ap.add_argument("--out", default=GOLDEN)
+    ap.add_argument("--out", help=f"default: {os.path.relpath(GOLDEN, ROOT)}, with --train {os.path.relpath(TRAIN_GOLDEN, ROOT)}")
+    ap.add_argument("--train", action="store_true", help="the training plans (TRAIN_CASES) instead of the inference plans")
     a = ap.parse_args()
     commit = a.commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
     unets, sigs = {}, {}
+    if a.train:
+        for name in a.cases or list(TRAIN_CASES):
+            sigs[name] = run_train_case(name, full_unet() if TRAIN_CASES[name]["unet"] == "full" else None)
+            print(f"{name}: {', '.join(f'{k} {len(v)}' for k, v in sigs[name]['recorders'].items())} launches, sha256 "
+                  f"{[s[:16] for s in sigs[name]['sha256']]}", flush=True)
+        with open(a.out or TRAIN_GOLDEN, "w") as f:
+            json.dump(pack_train(sigs, commit), f, separators=(",", ":"))
+            f.write("\n")
+        return
     for name in a.cases or list(CASES):
         kind = CASES[name]["unet"]
         if kind not in unets:
             unets[kind] = tiny_unet() if kind == "tiny" else full_unet()
         sigs[name] = run_case(name, unets[kind])
         print(f"{name}: {sigs[name]['launches_per_step']} launches per step, sha256 {sigs[name]['sha256'][:16]}", flush=True)
-    with open(a.out, "w") as f:
+    with open(a.out or GOLDEN, "w") as f:
         json.dump(pack(sigs, commit), f, separators=(",", ":"))
         f.write("\n")
 
