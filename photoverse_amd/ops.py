@@ -949,18 +949,25 @@ class Recorder:
         self._add(self.lib.pv_cfg_dpm_step_masked, _ptr(eps_u), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
                   float(guidance), _ptr(mask), _ptr(known), _ptr(noise), ch, hw, latents.numel())
 
-    def cfg_dpm_step_guided(self, eps_u, eps_i, eps_c, latents, x0_prev, coef, state, g_text, g_image=None, rescale=0.0, mask=None, known=None, noise=None):
-        """The solver step with separate guidance scales and ``guidance_rescale`` (``pv_cfg_dpm_step_guided``): ``eps_i`` = eps(uncond text, cond image
-        tokens) or None (then the two-term formula at ``g_text``); ``rescale`` in [0, 1] pulls the guided prediction's per-sample standard deviation
-        towards ``eps_c``'s; ``mask`` / ``known`` / ``noise`` (all or none) as in ``cfg_dpm_step_masked``.  latents fp32 (B, C, H, W) contiguous."""
+    def _solver_step_operands(self, eps, latents, x0_prev, coef, state, rng, mask, known, noise):
+        """What the guided / stochastic / PAG solver steps share: shapes, dtypes and contiguity of the operands (``eps``: the predictions, None where a
+        launcher takes none), and the tensors the launch reads by raw pointer onto ``keep``.  Returns (B, channels, pixels per channel)."""
         B, ch = latents.shape[0], latents.shape[1]
         hw = latents.numel() // (B * ch)
-        eps = [t for t in (eps_u, eps_i, eps_c) if t is not None]
+        eps = [t for t in eps if t is not None]
         opt = [t for t in (mask, known, noise) if t is not None]
         assert len(opt) in (0, 3), "mask, known and noise come together"
         assert all(t.is_contiguous() and t.dtype == torch.float32 for t in eps + opt + [latents, x0_prev])
         assert all(t.shape == latents.shape for t in eps + [x0_prev] + opt[1:]) and (not opt or mask.numel() == B * hw), [t.shape for t in eps + opt]
-        self.keep.extend(eps + opt + [latents, x0_prev, coef, state])
+        assert rng is None or (rng.dtype == torch.int32 and rng.numel() == 4 and rng.is_contiguous()), "rng: four int32 words"
+        self.keep.extend(eps + opt + [latents, x0_prev, coef, state] + ([rng] if rng is not None else []))
+        return B, ch, hw
+
+    def cfg_dpm_step_guided(self, eps_u, eps_i, eps_c, latents, x0_prev, coef, state, g_text, g_image=None, rescale=0.0, mask=None, known=None, noise=None):
+        """The solver step with separate guidance scales and ``guidance_rescale`` (``pv_cfg_dpm_step_guided``): ``eps_i`` = eps(uncond text, cond image
+        tokens) or None (then the two-term formula at ``g_text``); ``rescale`` in [0, 1] pulls the guided prediction's per-sample standard deviation
+        towards ``eps_c``'s; ``mask`` / ``known`` / ``noise`` (all or none) as in ``cfg_dpm_step_masked``.  latents fp32 (B, C, H, W) contiguous."""
+        B, ch, hw = self._solver_step_operands((eps_u, eps_i, eps_c), latents, x0_prev, coef, state, None, mask, known, noise)
         self._add(self.lib.pv_cfg_dpm_step_guided, _ptr(eps_u), _ptr(eps_i), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
                   float(g_text), float(g_text if g_image is None else g_image), float(rescale), _ptr(mask), _ptr(known), _ptr(noise), B, ch, hw)
 
@@ -969,15 +976,8 @@ class Recorder:
         """``cfg_dpm_step_guided`` as the step of SDE-DPM-Solver++(2M) (``pv_cfg_dpm_step_stochastic``): adds ``cn * z`` (``cn`` = column 7 of the
         coefficient row of an ``sde-dpmsolver++`` table) with ``z ~ N(0, I)`` generated in the kernel.  ``rng``: four int32 device words
         {seed_lo, seed_hi, sample_offset, stream} (uint32 bit patterns); the other arguments as ``cfg_dpm_step_guided``."""
-        B, ch = latents.shape[0], latents.shape[1]
-        hw = latents.numel() // (B * ch)
-        eps = [t for t in (eps_u, eps_i, eps_c) if t is not None]
-        opt = [t for t in (mask, known, noise) if t is not None]
-        assert len(opt) in (0, 3), "mask, known and noise come together"
-        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in eps + opt + [latents, x0_prev])
-        assert all(t.shape == latents.shape for t in eps + [x0_prev] + opt[1:]) and (not opt or mask.numel() == B * hw), [t.shape for t in eps + opt]
-        assert rng.dtype == torch.int32 and rng.numel() == 4 and rng.is_contiguous(), "rng: four int32 words"
-        self.keep.extend(eps + opt + [latents, x0_prev, coef, state, rng])
+        assert rng is not None, "rng: four int32 words"
+        B, ch, hw = self._solver_step_operands((eps_u, eps_i, eps_c), latents, x0_prev, coef, state, rng, mask, known, noise)
         self._add(self.lib.pv_cfg_dpm_step_stochastic, _ptr(eps_u), _ptr(eps_i), _ptr(eps_c), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
                   _ptr(rng), float(g_text), float(g_text if g_image is None else g_image), float(rescale), _ptr(mask), _ptr(known), _ptr(noise), B, ch, hw)
 
@@ -986,18 +986,28 @@ class Recorder:
         """``cfg_dpm_step_guided`` (``rng`` None) / ``cfg_dpm_step_stochastic`` (``rng`` given) with perturbed-attention guidance
         (``pv_cfg_dpm_step_pag``): ``eps_p`` = eps of the conditional forward with identity self-attention maps in the chosen layers; the prediction
         gains ``g_pag * (eps_c - eps_p)`` before the rescale.  ``eps_p`` None or ``g_pag`` 0: the bits of the other two launchers."""
-        B, ch = latents.shape[0], latents.shape[1]
-        hw = latents.numel() // (B * ch)
-        eps = [t for t in (eps_u, eps_i, eps_c, eps_p) if t is not None]
-        opt = [t for t in (mask, known, noise) if t is not None]
-        assert len(opt) in (0, 3), "mask, known and noise come together"
-        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in eps + opt + [latents, x0_prev])
-        assert all(t.shape == latents.shape for t in eps + [x0_prev] + opt[1:]) and (not opt or mask.numel() == B * hw), [t.shape for t in eps + opt]
-        assert rng is None or (rng.dtype == torch.int32 and rng.numel() == 4 and rng.is_contiguous()), "rng: four int32 words"
-        self.keep.extend(eps + opt + [latents, x0_prev, coef, state] + ([rng] if rng is not None else []))
+        B, ch, hw = self._solver_step_operands((eps_u, eps_i, eps_c, eps_p), latents, x0_prev, coef, state, rng, mask, known, noise)
         self._add(self.lib.pv_cfg_dpm_step_pag, _ptr(eps_u), _ptr(eps_i), _ptr(eps_c), _ptr(eps_p), _ptr(latents), _ptr(x0_prev), _ptr(coef), _ptr(state),
                   _ptr(rng), float(g_text), float(g_text if g_image is None else g_image), float(g_pag), float(rescale), _ptr(mask), _ptr(known),
                   _ptr(noise), B, ch, hw)
+
+    def solver_step(self, eps_u, eps_c, latents, x0_prev, coef, state, g_text, *, eps_i=None, eps_p=None, g_image=None, g_pag=0.0, rescale=0.0, rng=None,
+                    mask=None, known=None, noise=None):
+        """The CFG combine + solver step of a denoising loop: one launch, of the narrowest of the five launchers that takes what is given
+        (``pv_misc.hip``: the wider entry points land on the same kernel instantiations where an operand is absent, so the choice fixes the
+        launch list, not the bits): ``eps_p`` -> ``cfg_dpm_step_pag``; else ``rng`` -> ``_stochastic``; else ``eps_i`` or ``rescale`` > 0 ->
+        ``_guided``; else ``mask`` -> ``_masked``; else ``cfg_dpm_step``.  Arguments as in those methods."""
+        if eps_p is not None:
+            self.cfg_dpm_step_pag(eps_u, eps_i, eps_c, eps_p, latents, x0_prev, coef, state, g_text, g_image, g_pag, rescale, rng=rng, mask=mask,
+                                  known=known, noise=noise)
+        elif rng is not None:
+            self.cfg_dpm_step_stochastic(eps_u, eps_i, eps_c, latents, x0_prev, coef, state, rng, g_text, g_image, rescale, mask=mask, known=known, noise=noise)
+        elif eps_i is not None or rescale > 0.0:
+            self.cfg_dpm_step_guided(eps_u, eps_i, eps_c, latents, x0_prev, coef, state, g_text, g_image, rescale, mask=mask, known=known, noise=noise)
+        elif mask is not None:
+            self.cfg_dpm_step_masked(eps_u, eps_c, latents, x0_prev, coef, state, g_text, mask, known, noise)
+        else:
+            self.cfg_dpm_step(eps_u, eps_c, latents, x0_prev, coef, state, g_text)
 
     def composite_clamp(self, gen, orig, mask, lo, hi, out=None):
         """out = clamp(m * gen + (1 - m) * orig, lo, hi); gen / orig fp32 (B, C, H, W) contiguous, mask fp32 (B, 1, H, W); ``out`` may be ``gen``."""

@@ -30,6 +30,22 @@ _MERGE_MIN_ROWS = int(os.environ.get("PV_MERGE_MIN_ROWS", "8192"))
 
 
 class DenoiseLoop:
+    """One denoising step as launch plans over static buffers, captured into a HIP graph and replayed ``T`` times.
+
+    What runs beside what is data: ``self.schedule`` is a tuple of groups that run one after the other; a group is a tuple of lanes that run side by
+    side; a lane is a tuple of ``Recorder``s that run in order on one stream - lane 0 on the current stream, lane k on ``self._sides[k - 1]``, forked
+    after the previous group and joined before the next (a group of one lane issues no stream operation).  ``_step_eager`` walks it, eagerly or under
+    capture, where the lanes become the parallel branches of the graph.  Its contents, from the engine lists:
+
+    * one single-lane group per ``engines_p`` entry, the conditioning-independent prefix (``share_prefix``);
+    * with ``merge_lowres`` ``(u.rec_head | c.rec_head)``, ``(m.rec)``, ``(u.rec_tail | c.rec_tail)``: the high-resolution levels of the two CFG forwards side
+      by side around the ONE plan that runs their low-resolution levels and mid block over both forwards' samples;
+    * otherwise one group with a lane per whole forward, ``engines_u + engines_c + engines_i`` (each per sub-batch with ``batch_splits``); with ``pag_scale``
+      a conditional lane is ``(c.rec, p.rec)``, the perturbed forward right behind the conditional one whose trunk it may share;
+    * ``(tail)``: the CFG combine + solver step and the step counter's advance.
+
+    With ``two_streams=False`` every group's lanes are concatenated, in order, into its one lane."""
+
     def __init__(self, unet, batch: int, latent_size: int, n_ip: int, num_steps: int, guidance_scale: float,
                  scheduler: Optional[DPMSolverMultistepScheduler] = None, n_text: int = 77, use_graph: bool = True,
                  two_streams: bool = True, batch_splits: int = 1, training_mode: bool = False, fusion_seed: int = 0,
@@ -206,56 +222,42 @@ class DenoiseLoop:
                                        mid_in=half_in, mid_out=half_out, **kw, **side_by_side, **pre_kw))
             self.engines_m.append(unet.engine(2 * batch, latent_size, latent_size, n_ip, 1, text=text_all, ip=ip_all, segment="mid",
                                               mid_in=(mid_in, mid_in_cs), mid_out=(mid_out, mid_out_cs), **kw))
+
+        def engine(i, text, ip, out, **kw):
+            """the plan of sub-batch ``i`` of one forward: on its rows of the text and image-token buffers it reads and of the prediction it writes"""
+            return unet.engine(sb, latent_size, latent_size, n_ip, 1, text=text[i * sb * n_text:(i + 1) * sb * n_text],
+                               ip=ip[i * sb * n_ip:(i + 1) * sb * n_ip], out=out[i * sb:(i + 1) * sb], **kw)
+
         for i in range(0 if self.merge_lowres else batch_splits):
-            sl = slice(i * sb, (i + 1) * sb)
-            kw = dict(timesteps=self.timesteps, state=self.state, latents_in=self.latents[sl], n_text=n_text, freeu=self.freeu, **pre_kw)
+            kw = dict(timesteps=self.timesteps, state=self.state, latents_in=self.latents[i * sb:(i + 1) * sb], n_text=n_text, freeu=self.freeu, **pre_kw)
             if two_streams and batch_splits == 1:
                 kw.update(big_min=_SIDE_BIG_MIN)                    # the two whole forwards run side by side
             if training_mode:
                 kw.update(device_fusion="last_step")
             fs = dict(fusion_seed=fusion_seed * 4096 + 2 * i) if training_mode else {}
             fs2 = dict(fusion_seed=fusion_seed * 4096 + 2 * i + 1) if training_mode else {}
-            self.engines_u.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_u[i * sb * n_text:(i + 1) * sb * n_text],
-                                              ip=self.ip_u[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_u[sl], **kw, **fs))
-            self.engines_c.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_c[i * sb * n_text:(i + 1) * sb * n_text],
-                                              ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_c[sl], **kw, **fs2))
+            self.engines_u.append(engine(i, self.text_u, self.ip_u, self.eps_u, **kw, **fs))
+            self.engines_c.append(engine(i, self.text_c, self.ip_c, self.eps_c, **kw, **fs2))
             if three:
-                self.engines_i.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_u[i * sb * n_text:(i + 1) * sb * n_text],
-                                                  ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_m[sl], **kw))
+                self.engines_i.append(engine(i, self.text_u, self.ip_c, self.eps_m, **kw))
             if pag:
                 kwp = dict(kw)
                 if self.share_trunk:
                     kwp.update(trunk=self.engines_c[i])             # starts from the conditional plan's tensors (the prefix, if any, lies inside them)
                 elif "down_blocks.0.attentions.0" in self.pag_layers:
                     kwp.pop("prefix", None)                         # the prefix holds that transformer's UNperturbed attn1
-                self.engines_p_attn.append(unet.engine(sb, latent_size, latent_size, n_ip, 1, text=self.text_c[i * sb * n_text:(i + 1) * sb * n_text],
-                                                       ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], out=self.eps_p[sl], perturb=self.pag_layers,
-                                                       **kwp))
+                self.engines_p_attn.append(engine(i, self.text_c, self.ip_c, self.eps_p, perturb=self.pag_layers, **kwp))
         self.eng_u, self.eng_c = self.engines_u[0], self.engines_c[0]
         self.tail = Recorder(dev)
+        mask = known = noise = rng = None                 # static buffers only the loops of these modes have
         if self.inpaint:
-            self.mask = torch.ones((batch, 1, latent_size, latent_size), dtype=f32, device=dev)
-            self.known = torch.zeros_like(self.latents)
-            self.noise = torch.zeros_like(self.latents)
+            mask = self.mask = torch.ones((batch, 1, latent_size, latent_size), dtype=f32, device=dev)
+            known = self.known = torch.zeros_like(self.latents)
+            noise = self.noise = torch.zeros_like(self.latents)
         if self.stochastic:
-            self.rng = torch.zeros(4, dtype=torch.int32, device=dev)     # {seed_lo, seed_hi, sample_offset, stream} as uint32 bit patterns: set_noise_stream
-        if pag:
-            blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
-            self.tail.cfg_dpm_step_pag(self.eps_u, self.eps_m, self.eps_c, self.eps_p, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
-                                       self.image_guidance, self.pag_scale, self.guidance_rescale, rng=self.rng if self.stochastic else None, **blend)
-        elif self.stochastic:
-            blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
-            self.tail.cfg_dpm_step_stochastic(self.eps_u, self.eps_m, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.rng,
-                                              self.guidance, self.image_guidance, self.guidance_rescale, **blend)
-        elif three or self.guidance_rescale > 0.0:
-            blend = dict(mask=self.mask, known=self.known, noise=self.noise) if self.inpaint else {}
-            self.tail.cfg_dpm_step_guided(self.eps_u, self.eps_m, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
-                                          self.image_guidance, self.guidance_rescale, **blend)
-        elif self.inpaint:
-            self.tail.cfg_dpm_step_masked(self.eps_u, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance,
-                                          self.mask, self.known, self.noise)
-        else:
-            self.tail.cfg_dpm_step(self.eps_u, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance)
+            rng = self.rng = torch.zeros(4, dtype=torch.int32, device=dev)     # {seed_lo, seed_hi, sample_offset, stream} as uint32 bit patterns: set_noise_stream
+        self.tail.solver_step(self.eps_u, self.eps_c, self.latents, self.x0_prev, self.coef, self.state, self.guidance, eps_i=self.eps_m, eps_p=self.eps_p,
+                              g_image=self.image_guidance, g_pag=self.pag_scale, rescale=self.guidance_rescale, rng=rng, mask=mask, known=known, noise=noise)
         self.tail.step_advance(self.state)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.use_graph = use_graph
@@ -263,6 +265,19 @@ class DenoiseLoop:
         n_side = ((3 if three else 2) * batch_splits - 1) if two_streams else 0
         self._sides = [torch.cuda.Stream(device=dev) for _ in range(n_side)]
         self.launches_per_step = sum(len(e.rec) for e in self.all_engines) + len(self.tail)
+        # the step (class docstring): groups one after the other, a group's lanes side by side, a lane's recorders in order.  Recorders only
+        groups = [((e.rec,),) for e in self.engines_p]                   # the conditioning-independent prefix all forwards start from (share_prefix)
+        if self.merge_lowres:
+            (eu,), (ec,), (em,) = self.engines_u, self.engines_c, self.engines_m
+            groups += [((eu.rec_head,), (ec.rec_head,)), ((em.rec,),), ((eu.rec_tail,), (ec.rec_tail,))]
+        else:
+            # a lane per whole forward; the perturbed forward runs in its conditional forward's lane, right behind it (whose trunk it may share)
+            after = self._after_cond()
+            groups.append(tuple((e.rec, after[id(e)].rec) if id(e) in after else (e.rec,) for e in self.engines_u + self.engines_c + self.engines_i))
+        groups.append(((self.tail,),))
+        if not two_streams:
+            groups = [(sum(lanes, ()),) for lanes in groups]
+        self.schedule = tuple(groups)
 
     @property
     def all_engines(self):
@@ -319,62 +334,23 @@ class DenoiseLoop:
         self._host_step = start
 
     def _step_eager(self):
-        for e in self.engines_p:                       # the conditioning-independent prefix both branches start from (share_prefix)
-            e.rec.run()
-        if self.merge_lowres:
-            # head_u || head_c -> merged low-resolution part (both branches' samples as one batch) -> tail_u || tail_c -> CFG + solver step
-            (eu,), (ec,), (em,) = self.engines_u, self.engines_c, self.engines_m
-            main = torch.cuda.current_stream()
-            side = self._sides[0] if self.two_streams else None
-            if side is not None:
+        """One step, as ``self.schedule`` spells it.  A group of several lanes forks lanes 1.. onto the side streams (parallel branches of the captured
+        graph, so the small low-resolution launches of one forward overlap the others') and joins them before the next group starts."""
+        main = torch.cuda.current_stream()
+        for lanes in self.schedule:
+            sides = self._sides[:len(lanes) - 1]
+            for side, lane in zip(sides, lanes[1:]):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    ec.rec_head.run()
-                eu.rec_head.run()
+                    for rec in lane:
+                        rec.run()
+            for rec in lanes[0]:
+                rec.run()
+            for side in sides:
                 main.wait_stream(side)
-            else:
-                eu.rec_head.run()
-                ec.rec_head.run()
-            em.rec.run()
-            if side is not None:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    ec.rec_tail.run()
-                eu.rec_tail.run()
-                main.wait_stream(side)
-            else:
-                eu.rec_tail.run()
-                ec.rec_tail.run()
-            self.tail.run()
-            return
-        if self.two_streams:
-            # the forwards of a step (uncond, cond, with image_guidance_scale the image-only one; each per sub-batch) are independent until the
-            # CFG combine: fork them onto HIP streams (parallel branches of the captured graph) so the small low-resolution launches of one
-            # overlap the others'; joined before the combine
-            main = torch.cuda.current_stream()
-            engines = self.engines_u + self.engines_c + self.engines_i
-            after = self._after_cond()
-            for side, eng in zip(self._sides, engines[1:]):
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    eng.rec.run()
-                    if id(eng) in after:                # the perturbed forward: same stream, right behind its conditional forward
-                        after[id(eng)].rec.run()
-            engines[0].rec.run()
-            if id(engines[0]) in after:
-                after[id(engines[0])].rec.run()
-            for side in self._sides:
-                main.wait_stream(side)
-        else:
-            after = self._after_cond()
-            for e in self.engines_u + self.engines_c + self.engines_i:
-                e.rec.run()
-                if id(e) in after:
-                    after[id(e)].rec.run()
-        self.tail.run()
 
     def _after_cond(self):
-        """conditional engine -> the perturbed engine that follows it on its stream (``pag_scale``; empty otherwise)"""
+        """conditional engine -> the perturbed engine that follows it in its lane (``pag_scale``; empty otherwise)"""
         return {id(c): p for c, p in zip(self.engines_c, self.engines_p_attn)}
 
     def capture(self):

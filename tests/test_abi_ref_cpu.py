@@ -414,12 +414,20 @@ INFERENCE_MODULES = ("infer", "pipeline", "unet", "clip", "vae", "scheduler")
 
 def _inference_launchers():
     """Launchers the inference modules can record: the ``ops.Recorder`` methods they call on a recorder (``rec.<m>(`` / ``.tail.<m>(``), and the ``pv_*``
-    functions those methods add."""
+    functions those methods add - themselves or through the ``Recorder`` methods they call in turn (``solver_step`` picks one of five)."""
     import importlib
     import inspect
     import re
     from photoverse_amd.ops import Recorder
-    adds = {m: set(re.findall(r"_add\(\s*self\.lib\.(pv_\w+)", inspect.getsource(f))) for m, f in inspect.getmembers(Recorder, inspect.isfunction)}
+    source = {m: inspect.getsource(f) for m, f in inspect.getmembers(Recorder, inspect.isfunction)}
+    adds = {m: set(re.findall(r"_add\(\s*self\.lib\.(pv_\w+)", src)) for m, src in source.items()}
+    grew = True
+    while grew:                                          # to the fixed point: a method adds what the methods it calls on ``self`` add
+        grew = False
+        for m, src in source.items():
+            more = set().union(*(adds.get(c, set()) for c in re.findall(r"self\.(\w+)\(", src))) - adds[m]
+            adds[m] |= more
+            grew = grew or bool(more)
     found = set()
     for mod in INFERENCE_MODULES:
         src = inspect.getsource(importlib.import_module(f"photoverse_amd.{mod}"))

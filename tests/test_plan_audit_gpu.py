@@ -78,9 +78,11 @@ def _audit_loop(aud, plan, loop, seed, prepare=None):
         (eu,), (ec,), (em,) = loop.engines_u, loop.engines_c, loop.engines_m
         step += [eu.rec_head, ec.rec_head, em.rec, eu.rec_tail, ec.rec_tail]
     else:
-        after = loop._after_cond()
+        after = {id(c): p for c, p in zip(loop.engines_c, loop.engines_p_attn)}
         for e in loop.engines_u + loop.engines_c + loop.engines_i:
             step += [e.rec] + ([after[id(e)].rec] if id(e) in after else [])
+    flat = [rec for group in loop.schedule for lane in group for rec in lane]
+    assert len(flat) == len(step) + 1 and all(a is b for a, b in zip(flat, step + [loop.tail])), "this order is not the loop's schedule, flattened"
     for r in step:
         run("step1", r)
     run("tail1", loop.tail)

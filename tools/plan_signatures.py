@@ -8,6 +8,10 @@ launch list or the bits - from a checkout of the commit that is to be the refere
 
 ``--train``: the same for the training plans - every recorder of the ``TrainStep``s in ``TRAIN_CASES``, their dropout sites and fusion names, the sha256 of
 loss and gradients after an eager and after a replayed step - to ``tests/golden/train_plan_signatures.json`` (``tests/test_train_plan_signatures_gpu.py``).
+
+``--trace``: what one ``DenoiseLoop._step_eager()`` of every loop in ``TRACE_CASES`` issues, in order - recorder runs and stream waits with their streams,
+logged instead of launched - and how many streams a build and a ``capture()`` construct, to ``tests/golden/step_traces.json``
+(``tests/test_step_schedule_gpu.py``).  It reads only the engine lists, ``tail`` and ``_sides`` of a loop, so it records a commit that has no ``schedule``.
 """
 import argparse
 import hashlib
@@ -153,6 +157,79 @@ def unpack(doc: dict) -> dict:
     return cases
 
 
+# ---------------------------------------------------------------------------------------------------------------- the step's order
+TRACE_GOLDEN = os.path.join(ROOT, "tests", "golden", "step_traces.json")
+#: the loops of ``CASES`` (the bare engines have no step).  Only plans are built, so the full-size loops shrink to B = 1 at 32 x 32 (their P stays)
+TRACE_CASES = {name: dict(c, **(dict(B=1, S=32) if c["unet"] == "full" else {})) for name, c in CASES.items() if "kw" in c}
+
+
+class _CountedStream(torch.cuda.Stream):
+    """Counts the streams taken from torch's pool (``torch.cuda.current_stream()`` wraps an existing one by id: not counted)."""
+    built = 0
+
+    def __new__(cls, *a, **kw):
+        _CountedStream.built += "stream_id" not in kw and "stream_ptr" not in kw
+        return super().__new__(cls, *a, **kw)
+
+
+class _NoGraph:
+    """Stands in for ``torch.cuda.CUDAGraph`` and ``torch.cuda.graph`` while ``capture()`` is walked without capturing."""
+
+    def __init__(self, *a, **kw):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
+def recorder_labels(loop) -> dict:
+    """id(recorder) -> ``engines_u[0].rec`` ... / ``tail``: every recorder a step may run, named by where the loop holds it."""
+    labels = {id(loop.tail): "tail"}
+    for lst in ("engines_u", "engines_c", "engines_m", "engines_p", "engines_i", "engines_p_attn"):
+        for i, e in enumerate(getattr(loop, lst)):
+            for k in ("rec", "rec_head", "rec_tail"):
+                if getattr(e, k) is not None:
+                    labels[id(getattr(e, k))] = f"{lst}[{i}].{k}"
+    return labels
+
+
+def step_trace(loop) -> list:
+    """What one ``loop._step_eager()`` issues, in order, with nothing launched: ``["run", stream, recorder label]`` and ``["wait", waiting stream,
+    awaited stream]`` - stream 0 is the current stream, k is ``loop._sides[k - 1]``."""
+    from unittest import mock
+    from photoverse_amd.ops import Recorder
+    labels = recorder_labels(loop)
+    streams = [torch.cuda.current_stream().cuda_stream] + [s.cuda_stream for s in loop._sides]
+    assert len(set(streams)) == len(streams), "two of the loop's streams are one stream"
+    log = []
+    with mock.patch.object(Recorder, "run", lambda rec, stream=None: log.append(["run", streams.index(torch.cuda.current_stream().cuda_stream), labels[id(rec)]])), \
+            mock.patch.object(torch.cuda.Stream, "wait_stream", lambda s, other: log.append(["wait", streams.index(s.cuda_stream), streams.index(other.cuda_stream)])):
+        loop._step_eager()
+    return log
+
+
+def trace_case(name: str, unet):
+    """Build the loop of ``TRACE_CASES[name]`` and return (it, its trace record): ``step_trace`` and how many ``torch.cuda.Stream``s the build and a
+    ``capture()`` construct (torch hands streams out of a fixed pool in turn: the count decides which later loops share one).  ``capture()`` is walked with the
+    recorders, the stream waits and the graph replaced, so it launches and captures nothing; the loop is as built afterwards."""
+    from unittest import mock
+    from photoverse_amd.ops import Recorder
+    from photoverse_amd.pipeline import DenoiseLoop
+    c = TRACE_CASES[name]
+    with mock.patch.object(torch.cuda, "Stream", _CountedStream):
+        _CountedStream.built = 0
+        loop = DenoiseLoop(unet, c["B"], c["S"], c["P"], c["steps"], 7.5, **c["kw"])
+        built = _CountedStream.built
+        with mock.patch.object(Recorder, "run", lambda rec, stream=None: None), mock.patch.object(torch.cuda, "CUDAGraph", _NoGraph), \
+                mock.patch.object(torch.cuda, "graph", _NoGraph), mock.patch.object(torch.cuda.Stream, "wait_stream", lambda s, other: None):
+            loop.capture()
+        loop.graph = None
+    return loop, dict(trace=step_trace(loop), streams_built=built, streams_capture=_CountedStream.built - built)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the training plans
 TRAIN_GOLDEN = os.path.join(ROOT, "tests", "golden", "train_plan_signatures.json")
 _TRAIN_TINY = dict(unet="tiny", B=2, S=16, E=3, lora_dropout=0.0, face=True, run=True)      # tests' test_training_step_is_bit_reproducible
@@ -252,9 +329,22 @@ def main():
     ap.add_argument("--commit", help="the commit this checkout is at (default: git rev-parse HEAD)")
     ap.add_argument("--out", help=f"default: {os.path.relpath(GOLDEN, ROOT)}, with --train {os.path.relpath(TRAIN_GOLDEN, ROOT)}")
     ap.add_argument("--train", action="store_true", help="the training plans (TRAIN_CASES) instead of the inference plans")
+    ap.add_argument("--trace", action="store_true", help="the step traces of the loops (TRACE_CASES) instead of the plan signatures")
     a = ap.parse_args()
     commit = a.commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
     unets, sigs = {}, {}
+    if a.trace:
+        for name in a.cases or list(TRACE_CASES):
+            kind = TRACE_CASES[name]["unet"]
+            if kind not in unets:
+                unets[kind] = tiny_unet() if kind == "tiny" else full_unet()
+            sigs[name] = trace_case(name, unets[kind])[1]
+            print(f"{name}: {len(sigs[name]['trace'])} stream operations and recorder runs, streams {sigs[name]['streams_built']} + "
+                  f"{sigs[name]['streams_capture']}", flush=True)
+        with open(a.out or TRACE_GOLDEN, "w") as f:
+            json.dump(dict(commit=commit, cases=sigs), f, indent=0, separators=(",", ":"))
+            f.write("\n")
+        return
     if a.train:
         for name in a.cases or list(TRAIN_CASES):
             sigs[name] = run_train_case(name, full_unet() if TRAIN_CASES[name]["unet"] == "full" else None)
