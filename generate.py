@@ -19,6 +19,10 @@ the identity, and the prediction pushed away from it - repairs eyes, teeth and s
 
 ``--freeu B1 B2 S1 S2`` (FreeU: in the first two decoder blocks the first half of the backbone's channels is scaled by ``B1`` / ``B2`` and the skip
 connection's lowest frequencies by ``S1`` / ``S2``; the authors' values for SD-1.5 are ``1.5 1.6 0.9 0.2``; no additional forward).
+
+``--controlnet_path DIR|random`` with ``--control_image_path`` (ControlNet: a pose, edge or depth map, resized to the working resolution and scaled to
+[0, 1], steers the layout; ``random`` is a ControlNet copied from the UNet with a seeded non-zero init of its zero convs, or with no image path a
+synthetic checkerboard - for smoke runs) and ``--controlnet_conditioning_scale``.
 """
 import argparse
 import os
@@ -69,6 +73,10 @@ parser.add_argument("--pag_layers", nargs="+", type=str, default=["mid_block"],
                     help="Transformers whose self-attention is perturbed: name prefixes (mid_block, up_blocks.1, down_blocks.0.attentions.0, ...) or all")
 parser.add_argument("--freeu", nargs=4, type=float, default=None, metavar=("B1", "B2", "S1", "S2"),
                     help="FreeU: backbone scales B1 B2 and skip low-frequency scales S1 S2 of the first two decoder blocks (SD-1.5: 1.5 1.6 0.9 0.2; default off)")
+parser.add_argument("--controlnet_path", type=str, default=None,
+                    help="Directory with a ControlNet's diffusion_pytorch_model.safetensors (diffusers layout), or 'random' (copied from the UNet, seeded non-zero zero convs and a seeded re-draw of the embedding's convs)")
+parser.add_argument("--control_image_path", type=str, default=None, help="The control image (pose / edges / depth); resized to 8 * latent_size, scaled to [0, 1]")
+parser.add_argument("--controlnet_conditioning_scale", type=float, default=1.0, help="Scale of the ControlNet's residuals (0 = off)")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -114,6 +122,30 @@ def prepare_mask(args):
     return preprocess_mask(Image.open(args.mask_image_path), size=8 * args.latent_size)[None]
 
 
+def prepare_control(args, unet):
+    """``--controlnet_path`` / ``--control_image_path`` -> (ControlNetModel on the UNet's device, control image (1, 3, H, W) in [0, 1]), or (None, None)."""
+    if args.controlnet_path is None:
+        if args.control_image_path is not None:
+            raise SystemExit("--control_image_path needs --controlnet_path")
+        return None, None
+    from photoverse_amd.controlnet import ControlNetModel
+    if args.controlnet_path == "random":
+        cn = ControlNetModel.from_unet(unet).randomize_zero_convs_(seed=0 if args.seed is None else args.seed)
+    else:
+        cn = ControlNetModel.from_pretrained(args.controlnet_path, **{k: v for k, v in vars(unet.config).items()})
+    side = 8 * args.latent_size
+    if args.control_image_path is not None:
+        from PIL import Image
+        from photoverse_amd.image_utils import preprocess_image
+        image = preprocess_image(Image.open(args.control_image_path).convert("RGB"), size=side, interpolation="bicubic")[None] * 0.5 + 0.5
+    elif args.controlnet_path == "random":
+        yy, xx = torch.meshgrid(torch.arange(side), torch.arange(side), indexing="ij")
+        image = (((yy // 32 + xx // 32) % 2).float())[None, None].repeat(1, 3, 1, 1)        # a checkerboard: something with edges for a smoke run
+    else:
+        raise SystemExit("--controlnet_path needs --control_image_path")
+    return cn.to(unet.device), image.clamp(0, 1).contiguous()
+
+
 if __name__ == "__main__":
     args = parser.parse_args()
     if not torch.cuda.is_available():
@@ -134,6 +166,7 @@ if __name__ == "__main__":
     for m in (vae, unet, text_encoder, image_encoder, image_adapter, text_adapter):
         m.to(device)
     example = prepare_example(args, tokenizer)
+    controlnet, control_image = prepare_control(args, unet)
     with torch.no_grad():
         out = run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler, device,
                             args.encoder_layers_idx, latent_size=args.latent_size, guidance_scale=args.guidance_scale,
@@ -142,7 +175,8 @@ if __name__ == "__main__":
                             hires_latent_size=args.hires_latent_size, hires_strength=args.hires_strength, hires_timesteps=args.hires_timesteps,
                             image_guidance_scale=args.image_guidance_scale, guidance_rescale=args.guidance_rescale,
                             sampler=args.sampler, pag_scale=args.pag_scale, pag_layers=tuple(args.pag_layers),
-                            freeu=None if args.freeu is None else tuple(args.freeu))
+                            freeu=None if args.freeu is None else tuple(args.freeu), controlnet=controlnet, control_image=control_image,
+                            controlnet_conditioning_scale=args.controlnet_conditioning_scale)
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

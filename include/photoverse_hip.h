@@ -610,6 +610,18 @@ int pv_resize_bilinear_affine_f32(const float* x, const float* y, const float* c
  * (batch*h*w rows of ld elements) below 2 GiB. */
 int pv_freeu_rows(const void* x, int32_t ldx, int32_t cx, void* x_out, int32_t ldxo, float b, const void* skip, int32_t lds, int32_t cs,
                   void* skip_out, int32_t ldso, float s, int32_t batch, int32_t h, int32_t w, void* stream);
+/* (ABI 19, a symbol added) [EXT] The small-channel 3x3 convs of a ControlNet's conditioning embedding (diffusers' ControlNetConditioningEmbedding):
+ *   out[(b*ho + oy)*wo + ox][co] = fp16(act(bias[co] + sum_{ky,kx,ci} in[b][oy*stride + ky - 1][ox*stride + kx - 1][ci] * w[co][(ky*3 + kx)*cin + ci]))
+ * pad 1 (taps outside the image are 0), stride 1 or 2, ho = (h - 1)/stride + 1, wo = (wd - 1)/stride + 1, fp32 accumulation; act = PV_ACT_NONE or
+ * PV_ACT_SILU.  w: fp16 [cout][9*cin], tap-major; bias: fp32 [cout]; out: fp16 rows with the leading dimension ldo.  Two input forms:
+ *   x_is_image = 1   x is fp32 NCHW [batch][cin][h][wd], contiguous, cin <= 4 (ldx is ignored): the first layer, on ordinary vector instructions;
+ *   x_is_image = 0   x is fp16 rows [batch*h*wd][cin] with the leading dimension ldx, cin % 8 == 0, cin <= 256: v_mfma_f32_16x16x32_f16 over the flat
+ *                    contraction k = tap*cin + ci, zero-filled to a multiple of 32.
+ * cout % 16 == 0, cout <= 256; ldo >= cout, ldx >= cin, both multiples of 8; w, bias, out (and x as rows) 16-byte aligned; x and out below 2 GiB each.
+ * Inputs are read only; out must not overlap x.  Anything else returns hipErrorInvalidValue before any HIP call.
+ * (Bound through _lib.EXT_SIGNATURES: the launcher is not yet in the launch audit's catalogue, which covers every `int pv_*` declaration of this header.) */
+int32_t pv_hint_conv3x3(const void* x, int32_t x_is_image, int32_t ldx, const void* w, const float* bias, void* out, int32_t ldo, int32_t batch,
+                        int32_t cin, int32_t cout, int32_t h, int32_t wd, int32_t stride, int32_t act, void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

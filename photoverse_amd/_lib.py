@@ -183,6 +183,15 @@ SIGNATURES = {
 }
 
 
+#: launchers that are NOT part of the launch audit's catalogue (``oracle/abi_ref.py`` places every name of ``SIGNATURES`` in its REF / NOT_AUDITED tables, and
+#: ``tests/test_host_cpu.py`` ties ``SIGNATURES`` to the header's ``int pv_*`` declarations): bound by ``load()`` like the others.  Their fp64 references live with
+#: their own tests (``pv_hint_conv3x3``: ``tests/test_controlnet_gpu.py``); the header declares them with the return type spelled ``int32_t``.  Moving a name
+#: from here into ``SIGNATURES`` goes together with its entry in the audit catalogue.
+EXT_SIGNATURES = {
+    "pv_hint_conv3x3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+}
+
+
 def kernel_info(fn, params):
     """(symbol, workgroups) of the launch ``fn`` (pv_gemm_conv_kernel_info / pv_attention_kernel_info) would make for ``params``: the library's own
     dispatch rule, asked - not restated - by the host side for its launch tags."""
@@ -219,7 +228,7 @@ def load():
         raise HipExtensionMissing(f"cannot load {LIB}: {e}") from e
     if lib.pv_abi_version() != ABI_VERSION:      # before the symbols are bound: a stale .so is told apart by its version, not by a missing symbol
         raise HipExtensionMissing(f"{LIB} has ABI {lib.pv_abi_version()}, expected {ABI_VERSION}: rebuild it")
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:     # a library of the same ABI number built before the symbol was added (pv_cfg_dpm_step_guided / _stochastic / _pag and pv_freeu_rows came without a new number)

@@ -31,6 +31,10 @@ and one term to the solver-step launch (``pv_cfg_dpm_step_pag``).
 And FreeU ([EXT] Si et al., CVPR 2024; diffusers' ``enable_freeu``): ``freeu=(b1, b2, s1, s2)`` re-weights the decoder's first two up blocks inside every
 forward - the first half of the backbone's channels times ``b``, the four lowest spatial frequencies of the skip connection times ``s`` - with one
 launch per ResnetBlock (``pv_freeu_rows``: the Fourier filter in closed form, no FFT) and no further forward or weights.
+
+And spatial control ([EXT] ControlNet, Zhang et al. 2023; diffusers' ``StableDiffusionControlNetPipeline``): ``controlnet`` + ``control_image`` run a
+``controlnet.ControlNetModel`` beside the UNet - its conditioning embedding once per call (``pv_hint_conv3x3``), its encoder twice per step - and add its
+zero-conv residuals to the UNet's skip connections and mid block output (``UNetEngine(control=...)``).
 """
 from __future__ import annotations
 
@@ -110,17 +114,21 @@ def _scheduler_for(scheduler, sampler) -> DPMSolverMultistepScheduler:
 
 
 def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False,
-              image_guidance=None, guidance_rescale=0.0, pag_scale=None, pag_layers=(), freeu=None) -> DenoiseLoop:
+              image_guidance=None, guidance_rescale=0.0, pag_scale=None, pag_layers=(), freeu=None, controlnet=None,
+              conditioning_scale=1.0) -> DenoiseLoop:
     cache = unet.__dict__.setdefault("_denoise_loops", OrderedDict())
     stochastic = bool(getattr(scheduler, "stochastic", False))      # the sampler: part of the key through the scheduler run_inference built for it
     key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed),
            None if image_guidance is None else float(image_guidance), float(guidance_rescale), stochastic,
            None if pag_scale is None else float(pag_scale), tuple(pag_layers), freeu, bool(inpaint))
+    if controlnet is not None:       # its identity, its weights' version and the scale; without one the key is what it was
+        key += (id(controlnet), controlnet.__dict__.get("_pack_version", 0), float(conditioning_scale))
     loop = cache.pop(key, None)
-    if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0):
+    if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0) or getattr(loop, "controlnet", None) is not controlnet:
         loop = DenoiseLoop(unet, batch, latent_size, n_ip, steps, guidance, scheduler=scheduler, training_mode=training_mode,
                            fusion_seed=fusion_seed, inpaint=inpaint, image_guidance_scale=image_guidance, guidance_rescale=guidance_rescale,
-                           stochastic=stochastic, pag_scale=pag_scale, pag_layers=tuple(pag_layers) or ("mid_block",), freeu=freeu)
+                           stochastic=stochastic, pag_scale=pag_scale, pag_layers=tuple(pag_layers) or ("mid_block",), freeu=freeu,
+                           **({} if controlnet is None else dict(controlnet=controlnet, conditioning_scale=conditioning_scale)))
         loop.unet_version = unet.__dict__.get("_pack_version", 0)
     cache[key] = loop                               # most recently used last
     while len(cache) > MAX_CACHED_LOOPS:
@@ -132,7 +140,8 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
                   image_guidance_scale=None, guidance_rescale=0.0, sampler="dpmsolver++", sample_offset=0, pag_scale=None, pag_layers=("mid_block",),
-                  freeu=None, inpaint_mask=None, paste_back=True, hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
+                  freeu=None, controlnet=None, control_image=None, controlnet_conditioning_scale=1.0, inpaint_mask=None, paste_back=True,
+                  hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
     global batch once and hands each rank its slice.
@@ -174,7 +183,30 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     ``(1.5, 1.6, 0.9, 0.2)``).  In the first two up blocks of every forward the first half of the backbone's channels is scaled by ``b1`` / ``b2`` and the
     skip connection's four lowest spatial frequencies by ``s1`` / ``s2``: more weight on the semantics, less high-frequency detail from the skips, at no
     additional forward.  ``(1, 1, 1, 1)`` is None: the plain call on the plain cached loop.  Holds for both passes of a hires run and combines with
-    every keyword above except ``training_mode``."""
+    every keyword above except ``training_mode``.
+
+    ``controlnet`` / ``control_image`` / ``controlnet_conditioning_scale`` (None: off; the two come together): a ``controlnet.ControlNetModel`` and its
+    control image (B or 1, 3, 8 * latent_size, 8 * latent_size) in [0, 1] - a pose, edge or depth map; a single image serves the whole batch.  The
+    ControlNet runs beside the UNet in every step, under the prompt and the negative prompt, and steers the layout through residuals on the UNet's skip
+    connections and mid block output, times ``controlnet_conditioning_scale`` (a finite number; 0 is the plain call on the plain cached loop).  Combines
+    with ``inpaint_mask``, ``strength``, ``sampler``, ``image_guidance_scale``, ``guidance_rescale``, ``pag_*`` and ``freeu``.  Not with ``training_mode``,
+    and not yet with ``hires_latent_size``: the second pass needs a second conditioning embedding at its own size (a follow-up)."""
+    if (controlnet is None) != (control_image is None):                                     # before any model is touched
+        raise ValueError("controlnet and control_image come together: got " + ("a controlnet without a control_image" if control_image is None else "a control_image without a controlnet"))
+    if not _is_finite_real(controlnet_conditioning_scale):
+        raise ValueError(f"controlnet_conditioning_scale must be a finite number, got {controlnet_conditioning_scale!r}")
+    if controlnet is not None:
+        if not _is_positive_int(latent_size):
+            raise ValueError(f"latent_size must be a positive int, got {latent_size!r}")
+        side = 8 * latent_size
+        if not torch.is_tensor(control_image) or control_image.dim() != 4 or tuple(control_image.shape[1:]) != (3, side, side):
+            raise ValueError(f"control_image must be a (B or 1, 3, {side}, {side}) tensor (8 x latent_size), got {tuple(getattr(control_image, 'shape', ()))}")
+        if float(controlnet_conditioning_scale) == 0.0:
+            controlnet = control_image = None          # off: the loop without it
+        elif training_mode:
+            raise ValueError("controlnet does not combine with training_mode=True")
+        elif hires_latent_size is not None:
+            raise ValueError("controlnet does not combine with hires_latent_size yet: the second pass needs a control embedding at its own size")
     freeu = normalize_freeu(freeu)                                                          # before any model is touched
     if freeu is not None and training_mode:
         raise ValueError("freeu does not combine with training_mode=True")
@@ -268,6 +300,8 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     start = strength_start(timesteps, float(strength))
     if start and not (from_noised_image or inpaint):
         raise ValueError("strength < 1 needs an image to start from: from_noised_image=True or an inpaint_mask")
+    if controlnet is not None and control_image.shape[0] not in (1, batch):
+        raise ValueError(f"control_image has batch {control_image.shape[0]}, expected {batch} or 1")
     if inpaint:
         pixel_mask, lat_mask = latent_mask(inpaint_mask, batch, latent_size)
         if tuple(pixel_mask.shape[2:]) != tuple(example["pixel_values"].shape[2:]):
@@ -299,8 +333,11 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                                           "concept_placeholder_idx": placeholder_idx})[0]
 
     loop = _loop_for(unet, batch, latent_size, encoder_hidden_states_image.shape[1], timesteps, guidance_scale, sch,     # :98-119
-                     training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint, **guide)
+                     training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint, **guide,
+                     controlnet=controlnet, conditioning_scale=float(controlnet_conditioning_scale))
     loop.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
+    if controlnet is not None:
+        loop.set_control(control_image)
     if inpaint:
         loop.set_inpaint(lat_mask.to(device), latents0, start_noise)
     if stochastic:

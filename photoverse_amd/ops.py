@@ -845,6 +845,32 @@ class Recorder:
                   tag=("freeu_rows_kernel", 26.0 * rows * cs + 0.5 * rows * cx, 2.0 * 2 * rows * (cx + cs)))
         return (xo if xo is not None else x), (so if so is not None else skip)
 
+    def hint_conv(self, x, w, bias, *, batch: int, h: int, wd: int, stride: int = 1, act: int = ACT_SILU, out=None):
+        """[EXT] One small-channel 3x3 conv (pad 1, ``stride`` 1 or 2) of a ControlNet's conditioning embedding (``pv_hint_conv3x3``) -> fp16 rows
+        ``[batch * ho * wo][cout]``.  ``x``: the fp32 NCHW image ``(batch, cin <= 4, h, wd)``, contiguous, or fp16 rows ``[batch * h * wd][cin]`` (a 2-D
+        row view, ``cin % 8 == 0``); ``w``: fp16 ``[cout][9 * cin]``, tap-major (``_conv3_w``); ``bias``: fp32 ``[cout]``."""
+        image = x.dim() == 4
+        if image:
+            assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape[0:1] + x.shape[2:]) == (batch, h, wd), (x.shape, batch, h, wd)
+            ldx, cin = 0, x.shape[1]
+        else:
+            assert x.dtype == torch.float16 and x.shape[0] == batch * h * wd, (x.shape, batch, h, wd)
+            ldx, cin = _rows(x)
+        cout = w.shape[0]
+        assert w.shape == (cout, 9 * cin) and w.dtype == torch.float16 and w.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == cout
+        ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
+        if out is None:
+            out = self.empty((batch * ho * wo, cout))
+        ldo, oc = _rows(out)
+        assert oc == cout and out.shape[0] == batch * ho * wo
+        self.colstats.pop((out.data_ptr(), out.shape[0], cout), None)
+        self.keep.extend((x, w, bias, out))
+        m = batch * ho * wo
+        self._add(self.lib.pv_hint_conv3x3, _ptr(x), int(image), ldx, _ptr(w), _ptr(bias), _ptr(out), ldo, batch, cin, cout, h, wd, int(stride), int(act),
+                  tag=("hint_conv_image_kernel" if image else "hint_conv_rows_kernel", 2.0 * m * cout * 9 * cin,
+                       (4.0 if image else 2.0) * batch * h * wd * cin + 2.0 * m * cout + 2.0 * cout * 9 * cin))
+        return out
+
     def posterior_sample(self, moments, eps, out=None):
         """moments fp32 [B, 2c, h, w] (mean | logvar), eps fp32 [B, c, h, w] -> mean + exp(0.5 clamp(logvar)) eps."""
         B, c2 = moments.shape[0], moments.shape[1]

@@ -42,6 +42,8 @@ class DenoiseLoop:
       by side around the ONE plan that runs their low-resolution levels and mid block over both forwards' samples;
     * otherwise one group with a lane per whole forward, ``engines_u + engines_c + engines_i`` (each per sub-batch with ``batch_splits``); with ``pag_scale``
       a conditional lane is ``(c.rec, p.rec)``, the perturbed forward right behind the conditional one whose trunk it may share;
+    * with ``controlnet``, in front of the forwards' group, ``(ctrl_u.rec | ctrl_c.rec)``: the ControlNet's plans under the uncond and the cond text, whose
+      control features the forwards read - the group join is the dependency;
     * ``(tail)``: the CFG combine + solver step and the step counter's advance.
 
     With ``two_streams=False`` every group's lanes are concatenated, in order, into its one lane."""
@@ -51,7 +53,8 @@ class DenoiseLoop:
                  two_streams: bool = True, batch_splits: int = 1, training_mode: bool = False, fusion_seed: int = 0,
                  merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False,
                  image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0, stochastic: bool = False,
-                 pag_scale: Optional[float] = None, pag_layers=("mid_block",), share_trunk: Optional[bool] = None, freeu=None):
+                 pag_scale: Optional[float] = None, pag_layers=("mid_block",), share_trunk: Optional[bool] = None, freeu=None,
+                 controlnet=None, conditioning_scale: float = 1.0):
         """``training_mode``: the reference enables grad on the LAST denoising step only (infer.py:99), where every cross-attention
         layer of both forwards then draws its branch fusion (attention_processor.py:413-420).  Here the draw runs on the device inside
         the captured step (``pv_fusion_draw`` keyed on the step counter), so the same graph serves all steps.  This is the forward semantics
@@ -112,7 +115,24 @@ class DenoiseLoop:
         keys (``unet.normalize_freeu``; all ones is None).  Every engine of the step is built with it (``UNetEngine(freeu=...)``) - uncond, cond,
         image-only, merged low-resolution part, prefix, perturbed: all forwards of a step see the same UNet - and records one ``pv_freeu_rows`` launch
         per ResnetBlock of the first two up blocks.  No further forward, stream or buffer; the tail is untouched.  None builds the loop described
-        above, launch for launch.  Combines with every mode above except ``training_mode``."""
+        above, launch for launch.  Combines with every mode above except ``training_mode``.
+
+        ``controlnet`` / ``conditioning_scale`` (beyond the reference; [EXT] ControlNet, diffusers' ``StableDiffusionControlNetPipeline``): a
+        ``controlnet.ControlNetModel`` on the UNet's device.  None, or a scale of 0, builds the loop described above, launch for launch.  Otherwise two
+        control plans per sub-batch (``engines_ctrl_u`` / ``engines_ctrl_c``: the ControlNet under ``text_u`` / ``text_c``) run per step in a group of
+        their own in front of the forwards, and every forward is built with ``UNetEngine(control=..., control_scale=conditioning_scale)``: uncond and
+        image-only forwards read the uncond control features, cond and perturbed forwards the cond ones (the ControlNet is not perturbed).  The
+        conditioning embedding of the control image (``hint_emb``, static fp16 [B * S * S][c0]) is computed once per generation by ``set_control``,
+        outside the captured step; it is zero until then.  ``merge_lowres`` is off in this mode, ``share_prefix`` still applies to the UNet plans.
+        Combines with every mode above except ``training_mode``."""
+        import math
+        if not (isinstance(conditioning_scale, numbers.Real) and not isinstance(conditioning_scale, bool) and math.isfinite(conditioning_scale)):
+            raise ValueError(f"conditioning_scale must be a finite number, got {conditioning_scale!r}")
+        self.conditioning_scale = float(conditioning_scale)
+        self.controlnet = controlnet if (controlnet is not None and self.conditioning_scale != 0.0) else None
+        ctrl = self.controlnet is not None
+        if ctrl and training_mode:
+            raise ValueError("controlnet does not combine with training_mode=True")
         from .unet import normalize_freeu
         self.freeu = normalize_freeu(freeu)                  # host-side, before the UNet is touched
         if self.freeu is not None and training_mode:
@@ -179,6 +199,7 @@ class DenoiseLoop:
         self.eps_m = torch.empty_like(self.latents) if three else None      # eps(uncond text, cond image tokens)
         self.eps_p = torch.empty_like(self.latents) if pag else None        # eps(cond) with perturbed self-attention
         self.engines_u, self.engines_c, self.engines_m, self.engines_p, self.engines_i, self.engines_p_attn = [], [], [], [], [], []
+        self.engines_ctrl_u, self.engines_ctrl_c = [], []
         if share_prefix is None:
             share_prefix = os.environ.get("PV_SHARE_PREFIX", "0") == "1"
         first = unet.down_blocks[0]
@@ -198,7 +219,7 @@ class DenoiseLoop:
             rows = 2 * batch * (latent_size >> split) ** 2
             # (... and at the launch-bound end, up to 1024 rows - bs = 1 / 2 at 64 x 64 latents - the merged plan's fewer launches win again: +1.0 % / +0.4 %)
             merge_lowres = (env != "0") if env is not None else (rows >= _MERGE_MIN_ROWS or rows <= 1024)
-        self.merge_lowres = bool(merge_lowres and not training_mode and not three and not pag and batch_splits == 1 and n_lv > split
+        self.merge_lowres = bool(merge_lowres and not training_mode and not three and not pag and not ctrl and batch_splits == 1 and n_lv > split
                                  and ((latent_size >> split) ** 2) % 64 == 0 and latent_size % (1 << (n_lv - 1)) == 0)
         if self.merge_lowres:
             # text / image-token buffers of the two branches are the halves of ONE buffer: the merged plan reads it whole
@@ -228,20 +249,39 @@ class DenoiseLoop:
             return unet.engine(sb, latent_size, latent_size, n_ip, 1, text=text[i * sb * n_text:(i + 1) * sb * n_text],
                                ip=ip[i * sb * n_ip:(i + 1) * sb * n_ip], out=out[i * sb:(i + 1) * sb], **kw)
 
+        if ctrl:
+            if controlnet.device != dev or tuple(controlnet.config.block_out_channels) != tuple(cfg.block_out_channels):
+                raise ValueError("controlnet must live on the UNet's device and have its block_out_channels")
+            from .controlnet import hint_plan
+            c0 = cfg.block_out_channels[0]
+            self.control_image = torch.zeros((batch, controlnet.config.conditioning_channels, 8 * latent_size, 8 * latent_size), dtype=f32, device=dev)
+            self.hint_emb = torch.zeros((batch * latent_size * latent_size, c0), dtype=f16, device=dev)
+            self.hint_rec = Recorder(dev)                           # once per generation (set_control), outside the captured step
+            hint_plan(self.hint_rec, controlnet.controlnet_cond_embedding, self.control_image, self.hint_emb)
         for i in range(0 if self.merge_lowres else batch_splits):
             kw = dict(timesteps=self.timesteps, state=self.state, latents_in=self.latents[i * sb:(i + 1) * sb], n_text=n_text, freeu=self.freeu, **pre_kw)
             if two_streams and batch_splits == 1:
                 kw.update(big_min=_SIDE_BIG_MIN)                    # the two whole forwards run side by side
+            ctl_u = ctl_c = {}
+            if ctrl:
+                rows = latent_size * latent_size
+                ckw = {k: v for k, v in kw.items() if k in ("timesteps", "state", "latents_in", "n_text", "big_min")}
+                for text, lst in ((self.text_u, self.engines_ctrl_u), (self.text_c, self.engines_ctrl_c)):
+                    # (the image-token buffer is only a shape here: the ControlNet's cross-attention is text-only, its image-token K / V weights are zero)
+                    lst.append(controlnet.control_engine(sb, latent_size, latent_size, n_ip, self.hint_emb[i * sb * rows:(i + 1) * sb * rows],
+                                                         text=text[i * sb * n_text:(i + 1) * sb * n_text], ip=self.ip_c[i * sb * n_ip:(i + 1) * sb * n_ip], **ckw))
+                ctl_u = dict(control=self.engines_ctrl_u[i], control_scale=self.conditioning_scale)
+                ctl_c = dict(control=self.engines_ctrl_c[i], control_scale=self.conditioning_scale)
             if training_mode:
                 kw.update(device_fusion="last_step")
             fs = dict(fusion_seed=fusion_seed * 4096 + 2 * i) if training_mode else {}
             fs2 = dict(fusion_seed=fusion_seed * 4096 + 2 * i + 1) if training_mode else {}
-            self.engines_u.append(engine(i, self.text_u, self.ip_u, self.eps_u, **kw, **fs))
-            self.engines_c.append(engine(i, self.text_c, self.ip_c, self.eps_c, **kw, **fs2))
+            self.engines_u.append(engine(i, self.text_u, self.ip_u, self.eps_u, **kw, **fs, **ctl_u))
+            self.engines_c.append(engine(i, self.text_c, self.ip_c, self.eps_c, **kw, **fs2, **ctl_c))
             if three:
-                self.engines_i.append(engine(i, self.text_u, self.ip_c, self.eps_m, **kw))
+                self.engines_i.append(engine(i, self.text_u, self.ip_c, self.eps_m, **kw, **ctl_u))     # uncond text: the uncond control features
             if pag:
-                kwp = dict(kw)
+                kwp = dict(kw, **ctl_c)                             # the perturbed forward reads the conditional control features
                 if self.share_trunk:
                     kwp.update(trunk=self.engines_c[i])             # starts from the conditional plan's tensors (the prefix, if any, lies inside them)
                 elif "down_blocks.0.attentions.0" in self.pag_layers:
@@ -271,6 +311,8 @@ class DenoiseLoop:
             (eu,), (ec,), (em,) = self.engines_u, self.engines_c, self.engines_m
             groups += [((eu.rec_head,), (ec.rec_head,)), ((em.rec,),), ((eu.rec_tail,), (ec.rec_tail,))]
         else:
+            if ctrl:
+                groups.append(tuple((e.rec,) for e in self.engines_ctrl_u + self.engines_ctrl_c))
             # a lane per whole forward; the perturbed forward runs in its conditional forward's lane, right behind it (whose trunk it may share)
             after = self._after_cond()
             groups.append(tuple((e.rec, after[id(e)].rec) if id(e) in after else (e.rec,) for e in self.engines_u + self.engines_c + self.engines_i))
@@ -283,7 +325,7 @@ class DenoiseLoop:
     def all_engines(self):
         """Every plan of a step (uncond / cond branches, with ``merge_lowres`` the merged low-resolution part, with ``image_guidance_scale`` the
         image-only branch, with ``pag_scale`` the perturbed branch)."""
-        return self.engines_u + self.engines_c + self.engines_m + self.engines_p + self.engines_i + self.engines_p_attn
+        return self.engines_u + self.engines_c + self.engines_m + self.engines_p + self.engines_i + self.engines_p_attn + self.engines_ctrl_u + self.engines_ctrl_c
 
     # ------------------------------------------------------------------
     def set_conditioning(self, cond: Tuple[torch.Tensor, torch.Tensor], uncond: Tuple[torch.Tensor, torch.Tensor]):
@@ -304,6 +346,18 @@ class DenoiseLoop:
         for src, dst, what in ((mask, self.mask, "mask"), (known, self.known, "known latents"), (noise, self.noise, "noise")):
             require_cuda(src, what)
             dst.copy_(src.to(torch.float32).expand(dst.shape))
+
+    def set_control(self, control_image: torch.Tensor):
+        """The control image of a ``controlnet`` loop: (B or 1, 3, 8 S, 8 S), values in [0, 1]; a single image is broadcast over the batch.  Runs the hint
+        plan - seven ``pv_hint_conv3x3`` launches and one ``pv_gemm_conv`` - once, into the static ``hint_emb`` the control plans read.  Contents only: the
+        captured graph stays valid."""
+        if self.controlnet is None:
+            raise RuntimeError("DenoiseLoop.set_control(): the loop was built without a controlnet (or with conditioning_scale=0)")
+        want = tuple(self.control_image.shape)
+        if not torch.is_tensor(control_image) or control_image.dim() != 4 or tuple(control_image.shape[1:]) != want[1:] or control_image.shape[0] not in (1, want[0]):
+            raise ValueError(f"control_image has shape {tuple(getattr(control_image, 'shape', ()))}, expected ({want[0]} or 1, {want[1]}, {want[2]}, {want[3]})")
+        self.control_image.copy_(control_image.to(device=self.control_image.device, dtype=torch.float32).expand(want))
+        self.hint_rec.run()
 
     def set_noise_stream(self, seed: int, sample_offset: int = 0, stream: int = 0):
         """The noise of a ``stochastic`` loop: ``seed`` (taken modulo 2^64) is the Philox key, ``sample_offset`` the global index of this loop's first
@@ -446,6 +500,8 @@ class PhotoVersePipeline:
             local = {k: (v[sl] if torch.is_tensor(v) and v.shape[:1] == (n,) else v) for k, v in example.items()}
             if torch.is_tensor(kw.get("inpaint_mask")) and kw["inpaint_mask"].shape[:1] == (n,):
                 kw["inpaint_mask"] = kw["inpaint_mask"][sl]                      # a per-sample mask goes with its samples; a (1, ...) mask is shared
+            if torch.is_tensor(kw.get("control_image")) and kw["control_image"].shape[:1] == (n,) and n != 1:
+                kw["control_image"] = kw["control_image"][sl]                    # likewise a per-sample control image
             if kw.get("seed") is not None:
                 # the noise of the GLOBAL batch is drawn once with the reference's generator semantics (infer.py:52-59: CPU global
                 # generator) on every rank and sliced, so sample i equals sample i of the seeded 1-GPU run

@@ -200,9 +200,10 @@ class Stage(NamedTuple):
     tcols: int = 0
 
 
-def unet_stages(unet) -> Tuple[Stage, ...]:
+def unet_stages(unet, encoder_only: bool = False) -> Tuple[Stage, ...]:
     """The forward of ``unet`` as the sequence of its launch groups, in execution order: THE walk both the inference plans (``UNetEngine._build``) and
-    the training tape (``train.TrainStep._unet_pass``) record.  Host-side: reads the module tree only (a CPU or ``meta`` model will do)."""
+    the training tape (``train.TrainStep._unet_pass``) record.  Host-side: reads the module tree only (a CPU or ``meta`` model will do).
+    ``encoder_only``: the walk ends behind ``mid_block.resnets.1`` - all a ``controlnet.ControlNetModel`` has, and what its plan records."""
     out, off = [], 0
 
     def add(kind, m, name, block, level, skip=0):
@@ -225,6 +226,8 @@ def unet_stages(unet) -> Tuple[Stage, ...]:
     add("resnet", mb.resnets[0], "mid_block.resnets.0", ("mid", 0), lvl)
     add("transformer", mb.attentions[0], "mid_block.attentions.0", ("mid", 0), lvl)
     add("resnet", mb.resnets[1], "mid_block.resnets.1", ("mid", 0), lvl)
+    if encoder_only:
+        return tuple(out)
     for bi, blk in enumerate(unet.up_blocks):
         for i, res in enumerate(blk.resnets):
             add("resnet", res, f"up_blocks.{bi}.resnets.{i}", ("up", bi), lvl, -1)
@@ -272,13 +275,16 @@ def plan_ranges(stages, segment: Optional[str] = None, split: int = 2, prefix: b
     """What a ``UNetEngine`` records, as ranges ``(first, last, adopts, writes)`` of ``stages`` (indices, ``last`` inclusive).  ``adopts``: the tensors
     of another plan the range starts from - None (the latents), ``"prefix"``, ``"mid_in"``, ``"mid_out"`` or ``"trunk"``; ``writes``: where its last
     launch writes - None (a buffer of its own), ``"prefix_out"``, ``"mid_in"`` or ``"mid_out"``.  ``prefix``: the plan is given another plan's
-    prefix; ``trunk_at``: the transformer a perturbed plan on a shared trunk starts at.  One range per recorder: ``"outer"`` has two.  Host-side."""
+    prefix; ``trunk_at``: the transformer a perturbed plan on a shared trunk starts at.  One range per recorder: ``"outer"`` has two.
+    ``"control"`` (a ControlNet's plan): conv_in ... ``mid_block.resnets.1`` of ``stages``, the whole or the encoder-only walk.  Host-side."""
     n = len(stages)
     start = (2, "prefix") if prefix else (0, None)     # a prefix-fed plan resumes inside stage 2, the first transformer, behind its attn1
     if trunk_at is not None:
         return ((next(i for i, st in enumerate(stages) if st.name == trunk_at), n - 1, "trunk", None),)
     if segment == "prefix":
         return ((0, 2, None, "prefix_out"),)
+    if segment == "control":
+        return ((0, next(i for i, st in enumerate(stages) if st.name == "mid_block.resnets.1"), None, None),)
     if segment is None:
         return ((start[0], n - 1, start[1], None),)
     n_up = stages[-1].block[1] + 1
@@ -364,7 +370,8 @@ class UNetEngine:
                  latents_in: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None,
                  ip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, device_fusion: Optional[str] = None,
                  fusion_seed: int = 0, segment: Optional[str] = None, split: int = 2, mid_in=None, mid_out=None, big_min: Optional[int] = None,
-                 prefix=None, perturb=(), trunk: Optional["UNetEngine"] = None, freeu=None):
+                 prefix=None, perturb=(), trunk: Optional["UNetEngine"] = None, freeu=None, hint: Optional[torch.Tensor] = None,
+                 control: Optional["UNetEngine"] = None, control_scale: float = 1.0):
         """``device_fusion``: None - branch weights (w_text, w_ip) are launch parameters patched by the host (``_set_fusion``);
         ``"always"`` - every forward draws them on the device (grad-mode semantics of attention_processor.py:413-420, graph-safe);
         ``"last_step"`` - drawn only when the loop state says this is the last denoising step (``run_inference(training_mode=True)``,
@@ -397,13 +404,30 @@ class UNetEngine:
         blocks every ResnetBlock's inputs go through ``Recorder.freeu`` right where the skip is popped: the first half of the backbone's channels times
         ``b``, the skip's four lowest spatial frequencies times ``s`` - one launch per ResnetBlock, out of place, so a perturbed plan that adopts this plan's
         skips (``trunk=``) finds them raw and filters them itself.  Every plan kind that records those blocks has the hook (whole, ``"mid"`` at batch 2B,
-        ``"outer"`` tail, prefix-fed, ``trunk=``).  None records exactly the plan described above."""
+        ``"outer"`` tail, prefix-fed, ``trunk=``).  None records exactly the plan described above.
+
+        ``segment="control"`` + ``hint`` ([EXT] ControlNet, Zhang et al. 2023; diffusers' ``ControlNetModel``): ``unet`` is a
+        ``controlnet.ControlNetModel`` - the UNet's encoder with weights of its own - and the plan is conv_in ... ``mid_block.resnets.1`` of the same walk.
+        conv_in's GEMM carries ``residual=hint``, the static fp16 ``[batch * h * w][c0]`` conditioning embedding; the plan ends with
+        ``control_skips`` (every pushed skip tensor, in push order) and ``control_mid``: the control features.  Cross-attention is text-only: the
+        dual-branch launchers run with zero image-token K / V weights, so the image branch is exactly 0 whatever ``ip`` holds.
+
+        ``control`` / ``control_scale`` (the UNet side): the control plan of the same step and shape.  At every skip pop, before FreeU, the skip becomes
+        ``skip + control_scale * zero_conv_k(control_skips[k])`` - ONE GEMM with the residual epilogue, ``k`` the skip's push index - and the mid block's
+        output ``x + control_scale * zero_conv_mid(control_mid)``; both out of place, so a ``trunk=`` plan adopts raw skips and adds the control at its own
+        pops.  Every whole, prefix-fed and ``trunk=`` plan has the hook; the plan must run after ``control``'s.  None records the plan described above."""
         self.freeu = normalize_freeu(freeu)
         if self.freeu is not None and len(unet.up_blocks) < 2:
             raise ValueError("freeu acts on the first two up blocks: this UNet has fewer")
         self.unet, self.B, self.H, self.W, self.P, self.NT = unet, batch, h, w, n_ip, n_text
-        if segment not in (None, "outer", "mid", "prefix"):
-            raise ValueError("segment must be None, 'outer', 'mid' or 'prefix'")
+        if segment not in (None, "outer", "mid", "prefix", "control"):
+            raise ValueError("segment must be None, 'outer', 'mid', 'prefix' or 'control'")
+        if (segment == "control") != (hint is not None) or (segment == "control" and (device_fusion is not None or prefix is not None or perturb or control is not None)):
+            raise ValueError("a control plan is segment='control' with its hint= embedding (host-side fusion weights, no prefix, perturb or control)")
+        if control is not None and (segment is not None or control.segment != "control" or (control.B, control.H, control.W) != (batch, h, w)):
+            raise ValueError("control= must be the control plan of the same shape, given to a whole, prefix-fed or trunk= plan")
+        self.hint, self.control, self.control_scale = hint, control, float(control_scale)
+        self.control_skips, self.control_mid = [], None
         if segment in ("outer", "mid") and (mid_in is None or mid_out is None or device_fusion is not None):
             raise ValueError("a plan segment needs the shared mid_in / mid_out buffers (and host-side fusion weights)")
         if (segment == "prefix" or prefix is not None) and (device_fusion is not None or segment == "mid"):
@@ -558,7 +582,11 @@ class UNetEngine:
         proc = a2.processor
         wkv = torch.cat([_f16(a2.to_k.weight), _f16(a2.to_v.weight)], 0).contiguous()
         kvt = self.rec_cond.gemm(self.text, wkv, rows_per_image=self.NT)
-        wkvip = torch.cat([_f16(proc.to_k_ip[0].weight), _f16(proc.to_v_ip[0].weight)], 0).contiguous()
+        if isinstance(proc, PhotoVerseAttnProcessor2_0):
+            wkvip = torch.cat([_f16(proc.to_k_ip[0].weight), _f16(proc.to_v_ip[0].weight)], 0).contiguous()
+        else:
+            # text-only attn2 (a ControlNet's): zero image-token K / V weights - zero value rows make the image branch exactly 0
+            wkvip = torch.zeros((2 * C, self.ip.shape[1]), dtype=torch.float16, device=self.ip.device)
         kvip = self.rec_cond.gemm(self.ip, wkvip, rows_per_image=self.P)
         vnorm = rec.empty((b, heads, self.P), torch.float32)
         self.vnorms[name] = vnorm
@@ -608,12 +636,21 @@ class UNetEngine:
         hs = rec.gemm(gg, _f16(blk.ff.net[2].weight), bias=_f32(blk.ff.net[2].bias), residual=hs, rows_per_image=n)
         return rec.gemm(hs, _conv1_w(m.proj_out.weight), bias=_f32(m.proj_out.bias), residual=x, rows_per_image=n, colstats=True)
 
+    def _add_control(self, k: Optional[int], x, hw: int):
+        """``x + control_scale * zero_conv(c)`` as one GEMM with the residual epilogue, out of place: ``k`` - the push index of the skip ``x`` (``c`` =
+        the control plan's k-th skip, ``controlnet_down_blocks.k``), None - the mid block's output (``controlnet_mid_block``)."""
+        cn, s = self.control.unet, self.control_scale
+        m, c = (cn.controlnet_mid_block, self.control.control_mid) if k is None else (cn.controlnet_down_blocks[k], self.control.control_skips[k])
+        assert c.shape == x.shape, (k, c.shape, x.shape)
+        wz = (s * m.weight.detach().float().reshape(m.weight.shape[0], -1)).to(torch.float16).contiguous()
+        return self.rec.gemm(c, wz, bias=(s * m.bias.detach().float()).contiguous(), residual=x, rows_per_image=hw, colstats=True)
+
     # ------------------------------------------------------------------ plan
     def _build(self):
         u, rec, B = self.unet, self.rec, self.B
         cfg = u.config
         c0 = cfg.block_out_channels[0]
-        stages = unet_stages(u)
+        stages = unet_stages(u, encoder_only=self.segment == "control")
         # time embedding: sinusoid -> linear_1+SiLU -> linear_2 (+SiLU, the only consumer is time_emb_proj(silu(emb))); every plan kind records its own
         te = rec.timestep_embedding(self.timesteps, self.state, self.t_rows, c0)
         e1 = rec.gemm(te, _f16(u.time_embedding.linear_1.weight), bias=_f32(u.time_embedding.linear_1.bias), act=ACT_SILU)
@@ -678,15 +715,19 @@ class UNetEngine:
                     # conv_in (cin = 4): im2col to K = 36 -> 64 (zero padded), then the MFMA GEMM
                     w_in = conv_in_weight(u)
                     cols = rec.im2col3x3(self.x_in, batch=B, cin=cfg.in_channels, h=h, wd=w, kpad=w_in.shape[1])
-                    x = rec.gemm(cols, w_in, bias=_f32(m.bias), rows_per_image=h * w, colstats=True)
+                    x = rec.gemm(cols, w_in, bias=_f32(m.bias), rows_per_image=h * w, colstats=True, residual=self.hint)
                 elif st.kind == "resnet":
                     sk = None
                     if st.skip < 0:
                         sk, sh, sw = skips.pop()
                         assert (sh, sw) == (h, w)
+                        if self.control is not None:
+                            sk = self._add_control(len(skips), sk, h * w)     # the stack holds every skip pushed before this one: its height is the push index
                         if self.freeu is not None and st.block[1] < 2:
                             x, sk = rec.freeu(x, sk, batch=B, h=h, w=w, b=self.freeu[st.block[1]], s=self.freeu[2 + st.block[1]])
                     x = self._resnet(m, x, sk, B, h, w, temb_all, st.toff)   # channel concat [x | skip] is never materialised
+                    if self.control is not None and st.name == "mid_block.resnets.1":
+                        x = self._add_control(None, x, h * w)
                 elif st.kind == "transformer":
                     if seg is None and not self.perturb:
                         self.trunk_points[st.name] = ((x, cs_of(x)), [(t, cs_of(t), sh, sw) for t, sh, sw in skips])
@@ -710,6 +751,9 @@ class UNetEngine:
                     x = rec.conv_out(xn, conv_out_weight(u), _f32(m.bias), batch=B, cin=c0, h=h, wd=w, cout=cfg.out_channels, out=self.out_buf)
                 if st.skip > 0 and not ends:
                     skips.append((x, h, w))
+        if seg == "control":
+            self.control_skips, self.control_mid = [t for t, _, _ in skips], x
+            del skips[:]
         assert seg == "prefix" or not skips, "every skip connection is consumed inside the plan segment that produced it"
         self.out = x
         if seg == "outer":
