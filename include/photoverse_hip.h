@@ -622,6 +622,21 @@ int pv_freeu_rows(const void* x, int32_t ldx, int32_t cx, void* x_out, int32_t l
  * (Bound through _lib.EXT_SIGNATURES: the launcher is not yet in the launch audit's catalogue, which covers every `int pv_*` declaration of this header.) */
 int32_t pv_hint_conv3x3(const void* x, int32_t x_is_image, int32_t ldx, const void* w, const float* bias, void* out, int32_t ldo, int32_t batch,
                         int32_t cin, int32_t cout, int32_t h, int32_t wd, int32_t stride, int32_t act, void* stream);
+/* (ABI 19, a symbol added) [EXT] Token downsampling (ToDo, Smith et al. 2024): the token grid of fp16 rows pooled by a factor f per side - the keys and
+ * values of a self-attention whose queries stay at full resolution.
+ *   x:    rows [batch*h*w] of cols columns with the row stride ldx (a column slice of a wider buffer: the [K | V] columns of a qkv row);
+ *   out:  rows [batch*hp*wp][cols] with the row stride ldo, hp = ceil(h / f), wp = ceil(w / f); row (b*hp + oy)*wp + ox is the block
+ *         y in [oy*f, min(oy*f + f, h)), x in [ox*f, min(ox*f + f, w)) of image b:
+ *   PV_POOL_AVG      fp16(sum of the block's in-bounds pixels / their count): fp32 sum in row-major order, one division, one rounding
+ *                    (F.avg_pool2d(ceil_mode=True, count_include_pad=False)); an edge block of a grid f does not divide averages what it has;
+ *   PV_POOL_NEAREST  the bits of the block's top-left pixel (y, x) = (oy*f, ox*f)   ([::f, ::f]).
+ * 2 <= f <= 8; cols % 8 == 0, ldx and ldo multiples of 8 and >= cols; both pointers 16-byte aligned; batch, h, w >= 1; x is read only and out must not be
+ * x; every extent (batch*h*w rows of ld elements) below 2 GiB.  Anything else returns hipErrorInvalidValue before any HIP call.
+ * (Bound through _lib.EXT_SIGNATURES, as pv_hint_conv3x3 is.) */
+#define PV_POOL_AVG 0
+#define PV_POOL_NEAREST 1
+int32_t pv_token_pool(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t cols, int32_t batch, int32_t h, int32_t w, int32_t f, int32_t mode,
+                      void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

@@ -185,11 +185,15 @@ SIGNATURES = {
 
 #: launchers that are NOT part of the launch audit's catalogue (``oracle/abi_ref.py`` places every name of ``SIGNATURES`` in its REF / NOT_AUDITED tables, and
 #: ``tests/test_host_cpu.py`` ties ``SIGNATURES`` to the header's ``int pv_*`` declarations): bound by ``load()`` like the others.  Their fp64 references live with
-#: their own tests (``pv_hint_conv3x3``: ``tests/test_controlnet_gpu.py``); the header declares them with the return type spelled ``int32_t``.  Moving a name
+#: their own tests (``pv_hint_conv3x3``: ``tests/test_controlnet_gpu.py``, ``pv_token_pool``: ``tests/test_kv_downsample_gpu.py``); the header declares them with the return type spelled ``int32_t``.  Moving a name
 #: from here into ``SIGNATURES`` goes together with its entry in the audit catalogue.
 EXT_SIGNATURES = {
     "pv_hint_conv3x3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "pv_token_pool": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
+
+#: ``mode`` of ``pv_token_pool`` (the header's PV_POOL_*)
+POOL_MODES = {"avg": 0, "nearest": 1}
 
 
 def kernel_info(fn, params):

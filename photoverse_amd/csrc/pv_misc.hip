@@ -873,6 +873,90 @@ extern "C" int pv_freeu_rows(const void* x, int32_t ldx, int32_t cx, void* x_out
     return PV_CHECK_LAUNCH();
 }
 
+namespace {
+// Token pooling of fp16 rows (header: pv_token_pool).  One lane owns 8 adjacent columns of one output pixel: chunk index fastest, so the lanes of a
+// wave read whole 16-byte pieces of consecutive addresses of one input row per (dy, dx) and write one output row contiguously.  F > 0: the block
+// side at compile time (the f * f loads of a lane unroll and are in flight together); F = 0: the run-time side.  AVG: fp32 sum over the in-bounds
+// pixels in row-major order, one division by their count, one rounding; otherwise the bits of the top-left pixel.  No LDS, no atomics.
+template <int F, bool AVG>
+__global__ __launch_bounds__(256) void token_pool_kernel(const half_t* __restrict__ x, int ldx, half_t* __restrict__ out, int ldo, int cpr, int h, int w,
+                                                         int hp, int wp, int f_rt, long lanes) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= lanes) return;
+    const int f = F > 0 ? F : f_rt;
+    const long pix = i / cpr;                              // (image * hp + oy) * wp + ox
+    const int c0 = (int)(i - pix * cpr) * 8;
+    const long row = pix / wp;                             // image * hp + oy
+    const int ox = (int)(pix - row * wp);
+    const long img = row / hp;
+    const int oy = (int)(row - img * hp);
+    const int y0 = oy * f, x0 = ox * f;
+    const half_t* src = x + ((img * h + y0) * w + x0) * ldx + c0;
+    half8_t o;
+    if (!AVG) {
+        o = *reinterpret_cast<const half8_t*>(src);
+    } else {
+        const int ny = min(f, h - y0), nx = min(f, w - x0);            // >= 1: y0 < h and x0 < w by hp = ceil(h / f), wp = ceil(w / f)
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (F > 0) {
+            // every load unconditional (an out-of-bounds pixel reads the block's last in-bounds one and counts 0), so all F * F are issued before the first add
+            half8_t v[F > 0 ? F * F : 1];
+#pragma unroll
+            for (int dy = 0; dy < F; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < F; ++dx)
+                    v[dy * F + dx] = *reinterpret_cast<const half8_t*>(src + ((long)min(dy, ny - 1) * w + min(dx, nx - 1)) * ldx);
+#pragma unroll
+            for (int dy = 0; dy < F; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < F; ++dx) {
+                    const bool in = dy < ny && dx < nx;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[e] += in ? (float)v[dy * F + dx][e] : 0.f;
+                }
+        } else {
+            for (int dy = 0; dy < ny; ++dy)
+                for (int dx = 0; dx < nx; ++dx) {
+                    const half8_t v = *reinterpret_cast<const half8_t*>(src + ((long)dy * w + dx) * ldx);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
+                }
+        }
+        const float cnt = (float)(ny * nx);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (half_t)(acc[e] / cnt);
+    }
+    *reinterpret_cast<half8_t*>(out + pix * ldo + c0) = o;
+}
+}  // namespace
+
+extern "C" int32_t pv_token_pool(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t cols, int32_t batch, int32_t h, int32_t w, int32_t f,
+                                 int32_t mode, void* stream) {
+    if (!x || !out || x == out) return (int)hipErrorInvalidValue;
+    if (cols <= 0 || (cols % 8) || (ldx % 8) || (ldo % 8) || ldx < cols || ldo < cols) return (int)hipErrorInvalidValue;
+    if (batch <= 0 || h <= 0 || w <= 0 || f < 2 || f > 8) return (int)hipErrorInvalidValue;
+    if (mode != PV_POOL_AVG && mode != PV_POOL_NEAREST) return (int)hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(x) % 16) || (reinterpret_cast<uintptr_t>(out) % 16)) return (int)hipErrorInvalidValue;
+    // rows of ld elements below 2 GiB = 2^30 halfs, checked factor by factor (the full product may not fit 64 bits); the output has no more rows than the input
+    const int64_t lim = (int64_t)1 << 30;
+    const int64_t rows = (int64_t)batch * h;
+    if (rows >= lim || rows * w >= lim || rows * w * ldx >= lim || rows * w * ldo >= lim) return (int)hipErrorInvalidValue;
+    const int hp = (h + f - 1) / f, wp = (w + f - 1) / f, cpr = cols / 8;
+    const int64_t lanes = (int64_t)batch * hp * wp * cpr;
+    const int64_t blocks = (lanes + 255) / 256;
+    if (blocks >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const half_t* xi = reinterpret_cast<const half_t*>(x);
+    half_t* oo = reinterpret_cast<half_t*>(out);
+#define PV_POOL_LAUNCH(F, AVG) \
+    hipLaunchKernelGGL((token_pool_kernel<F, AVG>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xi, ldx, oo, ldo, cpr, h, w, hp, wp, f, (long)lanes)
+    if (mode == PV_POOL_NEAREST) PV_POOL_LAUNCH(0, false);
+    else if (f == 2) PV_POOL_LAUNCH(2, true);
+    else if (f == 4) PV_POOL_LAUNCH(4, true);
+    else PV_POOL_LAUNCH(0, true);
+#undef PV_POOL_LAUNCH
+    return PV_CHECK_LAUNCH();
+}
+
 extern "C" int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream) {
     if (!moments || !eps || !out || batch <= 0 || chw <= 0) return (int)hipErrorInvalidValue;
     const long n = (long)batch * chw;

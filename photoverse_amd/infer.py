@@ -35,6 +35,10 @@ launch per ResnetBlock (``pv_freeu_rows``: the Fourier filter in closed form, no
 And spatial control ([EXT] ControlNet, Zhang et al. 2023; diffusers' ``StableDiffusionControlNetPipeline``): ``controlnet`` + ``control_image`` run a
 ``controlnet.ControlNetModel`` beside the UNet - its conditioning embedding once per call (``pv_hint_conv3x3``), its encoder twice per step - and add its
 zero-conv residuals to the UNet's skip connections and mid block output (``UNetEngine(control=...)``).
+
+And token downsampling ([EXT] ToDo, Smith et al. 2024): ``kv_downsample`` / ``hires_kv_downsample`` pool the keys and values of the chosen self-attention
+layers by a factor per side (``pv_token_pool``, one launch behind the layer's qkv projection) while every query still attends: the N^2 part of the
+high-resolution levels shrinks by the factor squared, approximately, with no weights changed.
 """
 from __future__ import annotations
 
@@ -46,7 +50,7 @@ import torch
 
 from .pipeline import DenoiseLoop
 from .scheduler import DPMSolverMultistepScheduler
-from .unet import normalize_freeu, resolve_pag_layers
+from .unet import KV_DOWNSAMPLE_METHODS, check_kv_downsample_factor, normalize_freeu, resolve_kv_downsample_layers, resolve_pag_layers
 
 
 #: captured loops kept per UNet (each holds two engines of static activations: ~4 GB at bs=16) - least recently used evicted
@@ -115,7 +119,7 @@ def _scheduler_for(scheduler, sampler) -> DPMSolverMultistepScheduler:
 
 def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, training_mode=False, fusion_seed=0, inpaint=False,
               image_guidance=None, guidance_rescale=0.0, pag_scale=None, pag_layers=(), freeu=None, controlnet=None,
-              conditioning_scale=1.0) -> DenoiseLoop:
+              conditioning_scale=1.0, kv_downsample=None) -> DenoiseLoop:
     cache = unet.__dict__.setdefault("_denoise_loops", OrderedDict())
     stochastic = bool(getattr(scheduler, "stochastic", False))      # the sampler: part of the key through the scheduler run_inference built for it
     key = (batch, latent_size, n_ip, steps, float(guidance), bool(training_mode), int(fusion_seed),
@@ -123,12 +127,16 @@ def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, traini
            None if pag_scale is None else float(pag_scale), tuple(pag_layers), freeu, bool(inpaint))
     if controlnet is not None:       # its identity, its weights' version and the scale; without one the key is what it was
         key += (id(controlnet), controlnet.__dict__.get("_pack_version", 0), float(conditioning_scale))
+    kv_kw = {}
+    if kv_downsample is not None:    # (factor, method, resolved names); without it the key is what it was
+        key += ("kv_downsample",) + tuple(kv_downsample)
+        kv_kw = dict(kv_downsample=kv_downsample[0], kv_downsample_method=kv_downsample[1], kv_downsample_layers=kv_downsample[2])
     loop = cache.pop(key, None)
     if loop is None or loop.unet_version != unet.__dict__.get("_pack_version", 0) or getattr(loop, "controlnet", None) is not controlnet:
         loop = DenoiseLoop(unet, batch, latent_size, n_ip, steps, guidance, scheduler=scheduler, training_mode=training_mode,
                            fusion_seed=fusion_seed, inpaint=inpaint, image_guidance_scale=image_guidance, guidance_rescale=guidance_rescale,
                            stochastic=stochastic, pag_scale=pag_scale, pag_layers=tuple(pag_layers) or ("mid_block",), freeu=freeu,
-                           **({} if controlnet is None else dict(controlnet=controlnet, conditioning_scale=conditioning_scale)))
+                           **({} if controlnet is None else dict(controlnet=controlnet, conditioning_scale=conditioning_scale)), **kv_kw)
         loop.unet_version = unet.__dict__.get("_pack_version", 0)
     cache[key] = loop                               # most recently used last
     while len(cache) > MAX_CACHED_LOOPS:
@@ -140,7 +148,8 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
                   image_guidance_scale=None, guidance_rescale=0.0, sampler="dpmsolver++", sample_offset=0, pag_scale=None, pag_layers=("mid_block",),
-                  freeu=None, controlnet=None, control_image=None, controlnet_conditioning_scale=1.0, inpaint_mask=None, paste_back=True,
+                  freeu=None, controlnet=None, control_image=None, controlnet_conditioning_scale=1.0, kv_downsample=None,
+                  kv_downsample_method="avg", kv_downsample_layers=None, hires_kv_downsample=None, inpaint_mask=None, paste_back=True,
                   hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
@@ -190,7 +199,34 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     ControlNet runs beside the UNet in every step, under the prompt and the negative prompt, and steers the layout through residuals on the UNet's skip
     connections and mid block output, times ``controlnet_conditioning_scale`` (a finite number; 0 is the plain call on the plain cached loop).  Combines
     with ``inpaint_mask``, ``strength``, ``sampler``, ``image_guidance_scale``, ``guidance_rescale``, ``pag_*`` and ``freeu``.  Not with ``training_mode``,
-    and not yet with ``hires_latent_size``: the second pass needs a second conditioning embedding at its own size (a follow-up)."""
+    and not yet with ``hires_latent_size``: the second pass needs a second conditioning embedding at its own size (a follow-up).
+
+    ``kv_downsample`` (None: off; an int in 2 ... 8) / ``kv_downsample_method`` / ``kv_downsample_layers`` / ``hires_kv_downsample``: token downsampling
+    (ToDo, Smith et al. 2024).  In the self-attention of the chosen transformers every query still attends, but to keys and values pooled by the factor
+    per side of the token grid: a quarter of that layer's attention work at 2, a sixteenth at 4, no further forward, no changed weight.  The result is
+    approximate.  ``kv_downsample_method``: ``"avg"`` (block means; the default here because it aliases less - the paper's own default is, as far as we
+    recall, nearest-neighbour) or ``"nearest"`` (the top-left token of every block).  ``kv_downsample_layers``: None - the transformers of the
+    highest-resolution level, first down block and last up block, where the token count is largest - or name prefixes / ``"all"`` as ``pag_layers``
+    takes them; an entry that selects nothing is a ``ValueError``.  ``hires_kv_downsample`` (needs ``hires_latent_size``): the factor of the second pass -
+    None: the same as ``kv_downsample``; 1: off in the second pass; else an int in 2 ... 8.  The intended use is an exact first pass and a pooled second
+    one, where self-attention dominates: ``kv_downsample=None, hires_kv_downsample=2``.  Combines with every keyword above except ``training_mode``."""
+    if kv_downsample is not None:                                                           # before any model is touched
+        check_kv_downsample_factor(kv_downsample, "kv_downsample")
+    if hires_kv_downsample is not None:
+        check_kv_downsample_factor(hires_kv_downsample, "hires_kv_downsample", allow_one=True)
+        if hires_latent_size is None:
+            raise ValueError("hires_kv_downsample needs hires_latent_size")
+    if kv_downsample_method not in KV_DOWNSAMPLE_METHODS:
+        raise ValueError(f"kv_downsample_method must be one of {KV_DOWNSAMPLE_METHODS}, got {kv_downsample_method!r}")
+    kv1 = None if kv_downsample is None else int(kv_downsample)
+    kv2 = kv1 if hires_kv_downsample is None else (None if int(hires_kv_downsample) == 1 else int(hires_kv_downsample))
+    if (kv1 is not None or kv2 is not None) and training_mode:
+        raise ValueError("kv_downsample does not combine with training_mode=True")
+    if kv_downsample_layers is not None and not isinstance(kv_downsample_layers, str):
+        try:
+            kv_downsample_layers = tuple(kv_downsample_layers)
+        except TypeError:
+            raise ValueError(f"kv_downsample_layers must be None, a string or a sequence of strings, got {kv_downsample_layers!r}") from None
     if (controlnet is None) != (control_image is None):                                     # before any model is touched
         raise ValueError("controlnet and control_image come together: got " + ("a controlnet without a control_image" if control_image is None else "a control_image without a controlnet"))
     if not _is_finite_real(controlnet_conditioning_scale):
@@ -234,6 +270,10 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     # the layers resolve against the UNet's module tree (names only; no weight, no launch): an unknown entry fails here, before any model runs
     pag_names = resolve_pag_layers(unet, pag_layers) if pag_scale is not None else ()
     guide = dict(image_guidance=image_guidance_scale, guidance_rescale=float(guidance_rescale), pag_scale=pag_scale, pag_layers=pag_names, freeu=freeu)
+    # (the same for the pooled layers: names only, also when no pass pools - an unknown entry is an error whatever the factors are)
+    kv_names = resolve_kv_downsample_layers(unet, kv_downsample_layers) if (kv1 is not None or kv2 is not None or kv_downsample_layers is not None) else ()
+    kv_pass1 = None if kv1 is None else (kv1, kv_downsample_method, kv_names)
+    kv_pass2 = None if kv2 is None else (kv2, kv_downsample_method, kv_names)
     hires = hires_latent_size is not None
     if hires:                                          # before anything else: the first pass must not run for a second one that cannot
         if not _is_positive_int(hires_latent_size):
@@ -334,7 +374,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
 
     loop = _loop_for(unet, batch, latent_size, encoder_hidden_states_image.shape[1], timesteps, guidance_scale, sch,     # :98-119
                      training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint, **guide,
-                     controlnet=controlnet, conditioning_scale=float(controlnet_conditioning_scale))
+                     controlnet=controlnet, conditioning_scale=float(controlnet_conditioning_scale), kv_downsample=kv_pass1)
     loop.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
     if controlnet is not None:
         loop.set_control(control_image)
@@ -350,7 +390,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         sch2 = _scheduler_for(scheduler, sampler)
         x_start, start2 = hires_start(latents, hires_noise.to(device), sch2, hires_steps, hires_strength)
         loop2 = _loop_for(unet, batch, hires_latent_size, encoder_hidden_states_image.shape[1], hires_steps, guidance_scale, sch2,
-                          fusion_seed=0 if seed is None else int(seed), **guide)
+                          fusion_seed=0 if seed is None else int(seed), **guide, kv_downsample=kv_pass2)
         loop2.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
         if stochastic:
             loop2.set_noise_stream(noise_seed, int(sample_offset), stream=1)

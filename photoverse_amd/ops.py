@@ -845,6 +845,28 @@ class Recorder:
                   tag=("freeu_rows_kernel", 26.0 * rows * cs + 0.5 * rows * cx, 2.0 * 2 * rows * (cx + cs)))
         return (xo if xo is not None else x), (so if so is not None else skip)
 
+    def token_pool(self, x, *, batch: int, h: int, w: int, factor: int, method: str = "avg", out=None) -> torch.Tensor:
+        """[EXT] The token grid of ``x`` - fp16 rows ``[batch * h * w][cols]``, a 2-D row view (a column slice will do) - pooled by ``factor`` per side ->
+        fp16 rows ``[batch * hp * wp][cols]``, ``hp = ceil(h / factor)``, ``wp = ceil(w / factor)`` (``pv_token_pool``): ``"avg"`` - the mean of every block's
+        in-bounds pixels, ``"nearest"`` - its top-left pixel.  The keys and values of a self-attention with ``kv_downsample``."""
+        if method not in _lib.POOL_MODES:
+            raise ValueError(f"token_pool method must be one of {tuple(_lib.POOL_MODES)}, got {method!r}")
+        factor = int(factor)
+        assert x.dtype == torch.float16 and x.shape[0] == batch * h * w, (x.shape, x.dtype, batch, h, w)
+        ldx, cols = _rows(x)
+        hp, wp = -(-h // factor), -(-w // factor)
+        if out is None:
+            out = self.empty((batch * hp * wp, cols))
+        ldo, oc = _rows(out)
+        assert out.dtype == torch.float16 and tuple(out.shape) == (batch * hp * wp, cols) and oc == cols, (out.shape, batch, hp, wp, cols)
+        self.colstats.pop((out.data_ptr(), out.shape[0], cols), None)
+        self.keep.extend((x, out))
+        # avg: one add per input element and one division per output element; bytes: the input read once (nearest: one pixel per block), the output written once
+        rd = batch * h * w if method == "avg" else batch * hp * wp
+        self._add(self.lib.pv_token_pool, _ptr(x), ldx, _ptr(out), ldo, cols, batch, h, w, factor, _lib.POOL_MODES[method],
+                  tag=("token_pool_kernel", (1.0 * batch * h * w * cols + batch * hp * wp * cols) if method == "avg" else 0.0, 2.0 * cols * (rd + batch * hp * wp)))
+        return out
+
     def hint_conv(self, x, w, bias, *, batch: int, h: int, wd: int, stride: int = 1, act: int = ACT_SILU, out=None):
         """[EXT] One small-channel 3x3 conv (pad 1, ``stride`` 1 or 2) of a ControlNet's conditioning embedding (``pv_hint_conv3x3``) -> fp16 rows
         ``[batch * ho * wo][cout]``.  ``x``: the fp32 NCHW image ``(batch, cin <= 4, h, wd)``, contiguous, or fp16 rows ``[batch * h * wd][cin]`` (a 2-D

@@ -54,7 +54,8 @@ class DenoiseLoop:
                  merge_lowres: Optional[bool] = None, share_prefix: Optional[bool] = None, inpaint: bool = False,
                  image_guidance_scale: Optional[float] = None, guidance_rescale: float = 0.0, stochastic: bool = False,
                  pag_scale: Optional[float] = None, pag_layers=("mid_block",), share_trunk: Optional[bool] = None, freeu=None,
-                 controlnet=None, conditioning_scale: float = 1.0):
+                 controlnet=None, conditioning_scale: float = 1.0, kv_downsample: Optional[int] = None, kv_downsample_method: str = "avg",
+                 kv_downsample_layers=None):
         """``training_mode``: the reference enables grad on the LAST denoising step only (infer.py:99), where every cross-attention
         layer of both forwards then draws its branch fusion (attention_processor.py:413-420).  Here the draw runs on the device inside
         the captured step (``pv_fusion_draw`` keyed on the step counter), so the same graph serves all steps.  This is the forward semantics
@@ -124,8 +125,27 @@ class DenoiseLoop:
         image-only forwards read the uncond control features, cond and perturbed forwards the cond ones (the ControlNet is not perturbed).  The
         conditioning embedding of the control image (``hint_emb``, static fp16 [B * S * S][c0]) is computed once per generation by ``set_control``,
         outside the captured step; it is zero until then.  ``merge_lowres`` is off in this mode, ``share_prefix`` still applies to the UNet plans.
-        Combines with every mode above except ``training_mode``."""
+        Combines with every mode above except ``training_mode``.
+
+        ``kv_downsample`` / ``kv_downsample_method`` / ``kv_downsample_layers`` (beyond the reference; [EXT] token downsampling, ToDo, Smith et al. 2024):
+        None builds the loop described above, launch for launch.  An int ``f`` in 2 ... 8: in the self-attention of the transformers
+        ``resolve_kv_downsample_layers(unet, kv_downsample_layers)`` selects (None: those of the highest-resolution level) every query still attends, but
+        the keys and values are the token grid pooled ``f`` per side (``"avg"``: block means, the default - it aliases less; ``"nearest"``: the top-left
+        token) - ``f * f`` times fewer score and P.V flops there, approximate, no weights changed.  Every engine of the step is built with it
+        (``UNetEngine(kv_downsample=...)``) - uncond, cond, image-only, merged low-resolution part, prefix, perturbed, both control plans: all forwards of
+        a step see the same UNet.  ``launches_per_step`` rises by one ``pv_token_pool`` per selected, unperturbed transformer per plan that records its
+        attn1; ``merge_lowres``, ``share_prefix`` and ``share_trunk`` keep their rules.  Combines with every mode above except ``training_mode``."""
         import math
+        from .unet import KV_DOWNSAMPLE_METHODS, check_kv_downsample_factor, resolve_kv_downsample_layers
+        if kv_downsample is not None:                        # host-side, before the UNet is touched
+            check_kv_downsample_factor(kv_downsample)
+            if training_mode:
+                raise ValueError("kv_downsample does not combine with training_mode=True")
+        if kv_downsample_method not in KV_DOWNSAMPLE_METHODS:
+            raise ValueError(f"kv_downsample_method must be one of {KV_DOWNSAMPLE_METHODS}, got {kv_downsample_method!r}")
+        #: what every engine of the step is built with: None, or (factor, method, transformer names)
+        self.kv_downsample = None if kv_downsample is None else (int(kv_downsample), kv_downsample_method,
+                                                                  resolve_kv_downsample_layers(unet, kv_downsample_layers))
         if not (isinstance(conditioning_scale, numbers.Real) and not isinstance(conditioning_scale, bool) and math.isfinite(conditioning_scale)):
             raise ValueError(f"conditioning_scale must be a finite number, got {conditioning_scale!r}")
         self.conditioning_scale = float(conditioning_scale)
@@ -207,7 +227,7 @@ class DenoiseLoop:
         pre_kw = {}
         if self.share_prefix:
             self.engines_p.append(unet.engine(batch, latent_size, latent_size, n_ip, 1, latents_in=self.latents, segment="prefix", timesteps=self.timesteps,
-                                              state=self.state, n_text=n_text, freeu=self.freeu))
+                                              state=self.state, n_text=n_text, freeu=self.freeu, kv_downsample=self.kv_downsample))
             pre_kw = dict(prefix=self.engines_p[0].prefix_out)
         n_lv = len(cfg.block_out_channels)
         split = int(os.environ.get("PV_MERGE_SPLIT", "2"))     # resolution levels that stay in the per-branch plans (A/B switch; 3 = only 8 x 8 + mid merged)
@@ -234,7 +254,7 @@ class DenoiseLoop:
             mid_in_cs = torch.zeros((2 * batch * n_in // 64, 2, c_in), dtype=f32, device=dev)
             mid_out = torch.empty((2 * batch * n_out, c_out), dtype=f16, device=dev)
             mid_out_cs = torch.zeros((2 * batch * n_out // 64, 2, c_out), dtype=f32, device=dev)
-            kw = dict(timesteps=self.timesteps, state=self.state, n_text=n_text, split=split, freeu=self.freeu)
+            kw = dict(timesteps=self.timesteps, state=self.state, n_text=n_text, split=split, freeu=self.freeu, kv_downsample=self.kv_downsample)
             side_by_side = dict(big_min=_SIDE_BIG_MIN) if two_streams else {}      # heads / tails of the two branches run concurrently: half the chip each
             for i, (text, ip, eps, lst) in enumerate(((self.text_u, self.ip_u, self.eps_u, self.engines_u), (self.text_c, self.ip_c, self.eps_c, self.engines_c))):
                 half_in = (mid_in[i * batch * n_in:(i + 1) * batch * n_in], mid_in_cs[i * batch * n_in // 64:(i + 1) * batch * n_in // 64])
@@ -259,13 +279,13 @@ class DenoiseLoop:
             self.hint_rec = Recorder(dev)                           # once per generation (set_control), outside the captured step
             hint_plan(self.hint_rec, controlnet.controlnet_cond_embedding, self.control_image, self.hint_emb)
         for i in range(0 if self.merge_lowres else batch_splits):
-            kw = dict(timesteps=self.timesteps, state=self.state, latents_in=self.latents[i * sb:(i + 1) * sb], n_text=n_text, freeu=self.freeu, **pre_kw)
+            kw = dict(timesteps=self.timesteps, state=self.state, latents_in=self.latents[i * sb:(i + 1) * sb], n_text=n_text, freeu=self.freeu, kv_downsample=self.kv_downsample, **pre_kw)
             if two_streams and batch_splits == 1:
                 kw.update(big_min=_SIDE_BIG_MIN)                    # the two whole forwards run side by side
             ctl_u = ctl_c = {}
             if ctrl:
                 rows = latent_size * latent_size
-                ckw = {k: v for k, v in kw.items() if k in ("timesteps", "state", "latents_in", "n_text", "big_min")}
+                ckw = {k: v for k, v in kw.items() if k in ("timesteps", "state", "latents_in", "n_text", "big_min", "kv_downsample")}
                 for text, lst in ((self.text_u, self.engines_ctrl_u), (self.text_c, self.engines_ctrl_c)):
                     # (the image-token buffer is only a shape here: the ControlNet's cross-attention is text-only, its image-token K / V weights are zero)
                     lst.append(controlnet.control_engine(sb, latent_size, latent_size, n_ip, self.hint_emb[i * sb * rows:(i + 1) * sb * rows],

@@ -300,26 +300,72 @@ def transformer_names(unet) -> Tuple[str, ...]:
     return tuple(st.name for st in unet_stages(unet) if st.kind == "transformer")
 
 
-def resolve_pag_layers(unet, layers=("mid_block",)) -> Tuple[str, ...]:
-    """The transformers whose self-attention perturbed-attention guidance perturbs ([EXT] diffusers' ``pag_applied_layers``): every entry of
-    ``layers`` selects the transformers whose name starts with it; ``"all"`` (the string, or as an entry) selects every one.  Returned in execution
-    order, each once.  An entry that selects nothing, or no entry at all, is a ``ValueError``.  Host-side: reads the module tree only."""
+def _resolve_layers(unet, layers, what: str) -> Tuple[str, ...]:
+    """The transformers ``layers`` selects (``resolve_pag_layers`` / ``resolve_kv_downsample_layers``; ``what`` names the keyword in the messages)."""
     names = transformer_names(unet)
     if isinstance(layers, str):
         layers = (layers,)
     try:
         layers = tuple(layers)
     except TypeError:
-        raise ValueError(f"pag_layers must be a string or a sequence of strings, got {layers!r}") from None
+        raise ValueError(f"{what} must be a string or a sequence of strings, got {layers!r}") from None
     if not layers or not all(isinstance(e, str) and e for e in layers):
-        raise ValueError(f"pag_layers must be non-empty strings, got {layers!r}")
+        raise ValueError(f"{what} must be non-empty strings, got {layers!r}")
     chosen = set()
     for e in layers:
         hit = names if e == "all" else [nm for nm in names if nm.startswith(e)]
         if not hit:
-            raise ValueError(f"pag_layers entry {e!r} selects no transformer of this UNet (there are: {', '.join(names)})")
+            raise ValueError(f"{what} entry {e!r} selects no transformer of this UNet (there are: {', '.join(names)})")
         chosen.update(hit)
     return tuple(nm for nm in names if nm in chosen)
+
+
+def resolve_pag_layers(unet, layers=("mid_block",)) -> Tuple[str, ...]:
+    """The transformers whose self-attention perturbed-attention guidance perturbs ([EXT] diffusers' ``pag_applied_layers``): every entry of
+    ``layers`` selects the transformers whose name starts with it; ``"all"`` (the string, or as an entry) selects every one.  Returned in execution
+    order, each once.  An entry that selects nothing, or no entry at all, is a ``ValueError``.  Host-side: reads the module tree only."""
+    return _resolve_layers(unet, layers, "pag_layers")
+
+
+KV_DOWNSAMPLE_METHODS = ("avg", "nearest")
+
+
+def resolve_kv_downsample_layers(unet, layers=None) -> Tuple[str, ...]:
+    """The transformers whose self-attention reads pooled keys and values (``kv_downsample``; [EXT] ToDo, Smith et al. 2024): name prefixes or ``"all"``,
+    as ``resolve_pag_layers`` takes them.  None - the default - is the transformers of the highest-resolution level, those of the first down block and of
+    the last up block: where the paper applies it and where the token count is largest.  An entry that selects nothing is a ``ValueError``.  Host-side."""
+    if layers is None:
+        top = tuple(st.name for st in unet_stages(unet) if st.kind == "transformer" and st.level == 0)
+        if not top:
+            raise ValueError("kv_downsample_layers: this UNet has no transformer at its highest-resolution level - name the layers")
+        return top
+    return _resolve_layers(unet, layers, "kv_downsample_layers")
+
+
+def check_kv_downsample_factor(factor, what: str = "kv_downsample", allow_one: bool = False) -> None:
+    """An int in 2 ... 8 (``pv_token_pool``'s range; with ``allow_one`` also 1), not a bool; else a ``ValueError`` naming ``what``."""
+    import numbers
+    lo = 1 if allow_one else 2
+    if not (isinstance(factor, numbers.Integral) and not isinstance(factor, bool) and lo <= int(factor) <= 8):
+        raise ValueError(f"{what} must be None or an int in {lo} ... 8, got {factor!r}")
+
+
+def normalize_kv_downsample(kv_downsample) -> Optional[Tuple[int, str, Tuple[str, ...]]]:
+    """``UNetEngine(kv_downsample=...)`` as ``(factor, method, names)`` or None for off: None, or a triple of an int in 2 ... 8, ``"avg"`` / ``"nearest"`` and
+    transformer names (``resolve_kv_downsample_layers``); no names is off.  Anything else is a ``ValueError``.  Host-side."""
+    if kv_downsample is None:
+        return None
+    try:
+        factor, method, names = kv_downsample
+        names = (names,) if isinstance(names, str) else tuple(names)
+    except (TypeError, ValueError):
+        raise ValueError(f"kv_downsample must be None or (factor, method, names), got {kv_downsample!r}") from None
+    check_kv_downsample_factor(factor, "kv_downsample factor")
+    if method not in KV_DOWNSAMPLE_METHODS:
+        raise ValueError(f"kv_downsample method must be one of {KV_DOWNSAMPLE_METHODS}, got {method!r}")
+    if not all(isinstance(nm, str) and nm for nm in names):
+        raise ValueError(f"kv_downsample names must be transformer names, got {names!r}")
+    return (int(factor), method, names) if names else None
 
 
 FREEU_KEYS = ("b1", "b2", "s1", "s2")
@@ -371,7 +417,7 @@ class UNetEngine:
                  ip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, device_fusion: Optional[str] = None,
                  fusion_seed: int = 0, segment: Optional[str] = None, split: int = 2, mid_in=None, mid_out=None, big_min: Optional[int] = None,
                  prefix=None, perturb=(), trunk: Optional["UNetEngine"] = None, freeu=None, hint: Optional[torch.Tensor] = None,
-                 control: Optional["UNetEngine"] = None, control_scale: float = 1.0):
+                 control: Optional["UNetEngine"] = None, control_scale: float = 1.0, kv_downsample=None):
         """``device_fusion``: None - branch weights (w_text, w_ip) are launch parameters patched by the host (``_set_fusion``);
         ``"always"`` - every forward draws them on the device (grad-mode semantics of attention_processor.py:413-420, graph-safe);
         ``"last_step"`` - drawn only when the loop state says this is the last denoising step (``run_inference(training_mode=True)``,
@@ -415,7 +461,15 @@ class UNetEngine:
         ``control`` / ``control_scale`` (the UNet side): the control plan of the same step and shape.  At every skip pop, before FreeU, the skip becomes
         ``skip + control_scale * zero_conv_k(control_skips[k])`` - ONE GEMM with the residual epilogue, ``k`` the skip's push index - and the mid block's
         output ``x + control_scale * zero_conv_mid(control_mid)``; both out of place, so a ``trunk=`` plan adopts raw skips and adds the control at its own
-        pops.  Every whole, prefix-fed and ``trunk=`` plan has the hook; the plan must run after ``control``'s.  None records the plan described above."""
+        pops.  Every whole, prefix-fed and ``trunk=`` plan has the hook; the plan must run after ``control``'s.  None records the plan described above.
+
+        ``kv_downsample`` ([EXT] token downsampling, ToDo, Smith et al. 2024): None, or ``(factor, method, names)`` - ``names`` as
+        ``resolve_kv_downsample_layers`` returns them.  In a named transformer the ``qkv`` launch stays as it is, ONE ``Recorder.token_pool`` launch pools
+        its ``[K | V]`` columns over the ``h x w`` token grid (``factor`` per side, ``"avg"`` or ``"nearest"``; ``to_k`` / ``to_v`` have no bias, so pooling the
+        projected rows is projecting the pooled rows), and attn1 runs with every query on ``ceil(h / factor) * ceil(w / factor)`` keys.  A transformer that is
+        also in ``perturb`` keeps its identity attention - there is no K / V to pool.  Every plan kind that records a named transformer's attn1 has the hook
+        (whole, ``"prefix"``, ``"outer"``, ``"mid"``, ``trunk=``, ``"control"``; a prefix-fed plan adopts the pooled attn1 of its prefix); a ``"control"`` plan
+        ignores the names of decoder blocks it does not have.  None, or no names, records exactly the plan described above."""
         self.freeu = normalize_freeu(freeu)
         if self.freeu is not None and len(unet.up_blocks) < 2:
             raise ValueError("freeu acts on the first two up blocks: this UNet has fewer")
@@ -433,6 +487,7 @@ class UNetEngine:
         if (segment == "prefix" or prefix is not None) and (device_fusion is not None or segment == "mid"):
             raise ValueError("the shared prefix exists for the inference plans of the two CFG branches")
         self.perturb = tuple(perturb)
+        self.kv_downsample = normalize_kv_downsample(kv_downsample)
         if (self.perturb or trunk is not None) and (segment is not None or device_fusion is not None):
             raise ValueError("perturbed self-attention exists for whole inference plans (no segment, host-side fusion weights)")
         if trunk is not None and not self.perturb:
@@ -564,7 +619,13 @@ class UNetEngine:
         else:
             n1 = rec.layernorm(hs, _f32(blk.norm1.weight), _f32(blk.norm1.bias), eps=blk.norm1.eps)
             qkv = rec.gemm(n1, wqkv, rows_per_image=n)
-        sa = rec.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], batch=b, heads=heads, nq=n, nk=n, d=d)
+        if self.kv_downsample is not None and name in self.kv_downsample[2]:
+            # token downsampling: every query attends, the keys and values are the token grid pooled per f x f block - one launch over qkv's [K | V] columns
+            f, method, _ = self.kv_downsample
+            kv = rec.token_pool(qkv[:, C:], batch=b, h=h, w=w, factor=f, method=method)
+            sa = rec.attention(qkv[:, :C], kv[:, :C], kv[:, C:], batch=b, heads=heads, nq=n, nk=kv.shape[0] // b, d=d)
+        else:
+            sa = rec.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], batch=b, heads=heads, nq=n, nk=n, d=d)
         hs = rec.gemm(sa, _f16(a1.to_out[0].weight), bias=_f32(a1.to_out[0].bias), residual=hs, rows_per_image=n)
         if stop_after_attn1:
             return hs
@@ -665,6 +726,10 @@ class UNetEngine:
         unknown = [nm for nm in self.perturb if nm not in names]
         if unknown:
             raise ValueError(f"perturb names no transformer of this UNet: {unknown}")
+        if self.kv_downsample is not None and seg != "control":      # (a control plan has the encoder only: the decoder's names are not its business)
+            unknown = [nm for nm in self.kv_downsample[2] if nm not in names]
+            if unknown:
+                raise ValueError(f"kv_downsample names no transformer of this UNet: {unknown}")
         first = u.down_blocks[0]
         if (seg == "prefix" or pre is not None) and not (first.has_attn and len(first.resnets) >= 1):
             raise ValueError("the shared prefix needs an attention down block first (conv_in -> ResnetBlock -> transformer block)")
