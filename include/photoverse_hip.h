@@ -637,6 +637,31 @@ int32_t pv_hint_conv3x3(const void* x, int32_t x_is_image, int32_t ldx, const vo
 #define PV_POOL_NEAREST 1
 int32_t pv_token_pool(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t cols, int32_t batch, int32_t h, int32_t w, int32_t f, int32_t mode,
                       void* stream);
+/* (ABI 19, symbols added) [EXT] The two launches self-attention guidance needs beyond a forward (SAG, Hong et al., ICCV 2023; diffusers'
+ * StableDiffusionSAGPipeline), bound through _lib.EXT_SIGNATURES as pv_hint_conv3x3 is.  Nothing records them into a plan yet.
+ *
+ * pv_attn_colmass: the attention each key receives, from the q and k rows pv_attention reads (fp16 rows with their own leading dimensions: column slices
+ * of a fused qkv buffer will do, a row offset goes through the pointers; head hd owns columns hd*d .. hd*d + d):
+ *   A[b][hd][i][j] = softmax_j(q[b][i][hd] . k[b][j][hd] / sqrt(d))          i < nq, j < nk
+ *   mass[b][j]     = (1 / heads) * sum_hd sum_i A[b][hd][i][j]               fp32 [batch][nk]; every row of A sums to 1, so sum_j mass[b][j] = nq
+ * Scores on v_mfma_f32_16x16x32_f16 (fp32 accumulation), softmax with the row maximum, probabilities and every sum in fp32.  No atomics; heads and query
+ * tiles are added in a fixed order: a graph replay gives the bits of an eager launch.  One launch, no scratch; q and k are read only.
+ * d in {40, 64, 80, 160}; 1 <= nq, nk <= 1024; batch, heads >= 1; ldq, ldk >= heads*d and multiples of 8; q and k 16-byte aligned; q and k below 2 GiB
+ * each.  Anything else returns hipErrorInvalidValue before any HIP call. */
+int32_t pv_attn_colmass(const void* q, int32_t ldq, const void* k, int32_t ldk, float* mass, int32_t batch, int32_t heads, int32_t nq, int32_t nk, int32_t d,
+                        void* stream);
+/* pv_sag_degrade: the input of SAG's degraded forward.  x, eps_base, x_deg fp32 NCHW [batch][channels][h][w], contiguous; mass fp32 [batch][mh*mw] (the
+ * column mass of an mh x mw token grid); (ca, cb) = columns 0, 1 of the coefficient row pv_cfg_dpm_step reads at the step index of `state`:
+ *   m[b][y][x]  = mass[b][((y*mh)/h)*mw + (x*mw)/w] > 1.0      integer nearest upsample, strict comparison, one mask for all channels
+ *   x0          = ca*x + cb*eps_base
+ *   blur        = per plane, the 9x9 Gaussian of sigma 1 (k1d[t] = exp(-t*t/2) / sum, t = -4 .. 4; k2d = outer(k1d, k1d); evaluated rows, then columns) on x0
+ *                 with reflect padding 4 (-1 -> 1, n -> n - 2)
+ *   x_deg       = m ? x + (1/ca)*(blur - x0) : x               the bits of x where the mask is off
+ * (== add_noise(m*blur + (1 - m)*x0, eps_base, t) of diffusers: sqrt(acp_t) = 1/ca.)  One launch; inputs and state are read only; x_deg must be neither x
+ * nor eps_base.  h, w >= 5 (the padding reflects inside the plane); batch, channels, mh, mw >= 1; any h != w and map sizes that do not divide the plane;
+ * every operand below 2 GiB.  Anything else returns hipErrorInvalidValue before any HIP call. */
+int32_t pv_sag_degrade(const float* x, const float* eps_base, const float* mass, const float* coef, const int32_t* state, float* x_deg, int32_t batch,
+                       int32_t channels, int32_t h, int32_t w, int32_t mh, int32_t mw, void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

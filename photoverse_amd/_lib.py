@@ -190,6 +190,9 @@ SIGNATURES = {
 EXT_SIGNATURES = {
     "pv_hint_conv3x3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "pv_token_pool": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    # the two launches of self-attention guidance (``tests/test_sag_gpu.py``)
+    "pv_attn_colmass": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "pv_sag_degrade": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 #: ``mode`` of ``pv_token_pool`` (the header's PV_POOL_*)

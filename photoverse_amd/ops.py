@@ -867,6 +867,39 @@ class Recorder:
                   tag=("token_pool_kernel", (1.0 * batch * h * w * cols + batch * hp * wp * cols) if method == "avg" else 0.0, 2.0 * cols * (rd + batch * hp * wp)))
         return out
 
+    def attn_colmass(self, q, k, *, batch: int, heads: int, nq: int, nk: int, d: int, out=None) -> torch.Tensor:
+        """[EXT] The attention each key receives (``pv_attn_colmass``; self-attention guidance): ``mass[b][j] = mean_heads sum_i softmax_j(q_i . k_j / sqrt d)``
+        -> fp32 ``[batch][nk]``, every row summing to ``nq``.  ``q`` / ``k``: the fp16 row views ``attention`` takes - ``[batch * nq][heads * d]`` and
+        ``[batch * nk][heads * d]``, column slices of the fused qkv buffer will do.  ``d`` in {40, 64, 80, 160}, ``nq``, ``nk`` <= 1024."""
+        assert q.dtype == torch.float16 and k.dtype == torch.float16 and q.shape[0] == batch * nq and k.shape[0] == batch * nk, (q.shape, k.shape, batch, nq, nk)
+        ldq, cq = _rows(q)
+        ldk, ck = _rows(k)
+        assert cq == heads * d and ck == heads * d, (cq, ck, heads, d)
+        if out is None:
+            out = self.empty((batch, nk), torch.float32)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (batch, nk), (out.shape, out.dtype, batch, nk)
+        self.keep.extend((q, k, out))
+        # the scores are formed twice (row statistics, then the column sums); bytes: q once, k twice (from L2), mass written once
+        self._add(self.lib.pv_attn_colmass, _ptr(q), ldq, _ptr(k), ldk, _ptr(out), batch, heads, nq, nk, d,
+                  tag=("attn_colmass_kernel", 4.0 * batch * heads * nq * nk * d, 2.0 * batch * heads * d * (nq + 2 * nk) + 4.0 * batch * nk))
+        return out
+
+    def sag_degrade(self, x, eps_base, mass, coef, state, *, mh: int, mw: int, out=None) -> torch.Tensor:
+        """[EXT] The input of self-attention guidance's degraded forward (``pv_sag_degrade``): ``x + (1 / ca) m (blur(x0) - x0)`` with ``x0 = ca x + cb eps_base``
+        from the step's coefficient row, ``blur`` the 9 x 9 Gaussian of sigma 1 with reflect padding and ``m`` = ``mass > 1`` on the ``mh x mw`` token grid,
+        nearest-upsampled to the latents.  ``x`` / ``eps_base`` / ``out``: fp32 (B, C, h, w) contiguous, h, w >= 5; ``mass``: fp32 (B, mh * mw)."""
+        B, ch, h, w = x.shape
+        if out is None:
+            out = self.empty(tuple(x.shape), torch.float32)
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (x, eps_base, mass, out))
+        assert eps_base.shape == x.shape and out.shape == x.shape and mass.numel() == B * mh * mw, (x.shape, eps_base.shape, out.shape, mass.shape, mh, mw)
+        self.keep.extend((x, eps_base, mass, coef, state, out))
+        n = x.numel()
+        # per pixel: x0 (2), 9 + 9 taps of the separable blur on the halo-extended tile (~2.25 x 2 x 9 + 2 x 9), the blend (3)
+        self._add(self.lib.pv_sag_degrade, _ptr(x), _ptr(eps_base), _ptr(mass), _ptr(coef), _ptr(state), _ptr(out), B, ch, h, w, int(mh), int(mw),
+                  tag=("sag_degrade_kernel", 64.0 * n, 4.0 * 3 * n + 4.0 * mass.numel()))
+        return out
+
     def hint_conv(self, x, w, bias, *, batch: int, h: int, wd: int, stride: int = 1, act: int = ACT_SILU, out=None):
         """[EXT] One small-channel 3x3 conv (pad 1, ``stride`` 1 or 2) of a ControlNet's conditioning embedding (``pv_hint_conv3x3``) -> fp16 rows
         ``[batch * ho * wo][cout]``.  ``x``: the fp32 NCHW image ``(batch, cin <= 4, h, wd)``, contiguous, or fp16 rows ``[batch * h * wd][cin]`` (a 2-D
