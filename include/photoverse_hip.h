@@ -662,6 +662,29 @@ int32_t pv_attn_colmass(const void* q, int32_t ldq, const void* k, int32_t ldk, 
  * every operand below 2 GiB.  Anything else returns hipErrorInvalidValue before any HIP call. */
 int32_t pv_sag_degrade(const float* x, const float* eps_base, const float* mass, const float* coef, const int32_t* state, float* x_deg, int32_t batch,
                        int32_t channels, int32_t h, int32_t w, int32_t mh, int32_t mw, void* stream);
+/* (ABI 19, symbols added) [EXT] The two launches a T2I-Adapter (Mou et al. 2023; diffusers' T2IAdapter / down_intrablock_additional_residuals) needs beyond
+ * the existing paths, bound through _lib.EXT_SIGNATURES as pv_hint_conv3x3 is.
+ *
+ * pv_add_feature_rows: the per-step launch - a static feature map added at the end of a down block:
+ *   out[r][c] = fp16(fmaf(s, f[r % feat_rows][c], x[r][c]))                 r < rows, c < cols; one fp32 fma, one rounding
+ *   s         = scale_tab ? scale_tab[step index of `state`] : scale        scale_tab: device fp32, one entry per schedule row; state: the loop's step
+ *                                                                           counter {step index, table rows, -, -}, the index clamped as everywhere
+ * x, f, out: fp16 rows with the leading dimensions ldx, ldf, ldo (column slices will do).  feat_rows divides rows: a plan at batch 2B, or a sub-batch whose
+ * f pointer is offset, reads the per-sample features.  With s == 0 out holds the bits of x and f is not read (it may hold NaN).
+ * colstats (optional): fp32 [ceil(rows/64)][2][cols], the sum and the sum of squares of the fp16-rounded outputs per 64-row block and column - the format
+ * of pv_gemm_params.colstats, for pv_groupnorm_stats_from_colstats; a partial last block sums the rows it has; with s == 0 they are x's statistics.  A
+ * workgroup owns whole 64-row blocks of its columns and adds in a fixed order: no atomics, the same bits on every launch.
+ * cols % 8 == 0; ldx, ldf, ldo multiples of 8 and >= cols; x, f, out 16-byte aligned; out is neither x nor f; scale_tab needs state; without scale_tab
+ * scale is finite; every extent below 2 GiB.  Anything else returns hipErrorInvalidValue before any HIP call. */
+int32_t pv_add_feature_rows(const void* x, int32_t ldx, const void* f, int32_t ldf, int32_t feat_rows, void* out, int32_t ldo, int32_t rows, int32_t cols,
+                            float scale, const float* scale_tab, const int32_t* state, float* colstats, void* stream);
+/* pv_pixel_unshuffle8: PixelUnshuffle(8) of an fp32 NCHW image [batch][channels][h][w] into fp16 rows [batch*(h/8)*(w/8)][channels*64] (leading dimension
+ * ldo): row (b*(h/8) + y)*(w/8) + x, column c*64 + i*8 + j is fp16(image[b][c][8y + i][8x + j]) - exact, the rounding of the input.  batch_stride: elements
+ * between two images; 0 reads one image for every sample.  channels in 1 ... 4; h % 8 == 0, w % 8 == 0; ldo % 8 == 0, ldo >= channels*64; batch_stride 0
+ * or a multiple of 4 and >= channels*h*w; image and out 16-byte aligned; every extent below 2 GiB.  Anything else returns hipErrorInvalidValue before
+ * any HIP call. */
+int32_t pv_pixel_unshuffle8(const float* image, int64_t batch_stride, void* out, int32_t ldo, int32_t batch, int32_t channels, int32_t h, int32_t w,
+                            void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

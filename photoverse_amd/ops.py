@@ -926,6 +926,57 @@ class Recorder:
                        (4.0 if image else 2.0) * batch * h * wd * cin + 2.0 * m * cout + 2.0 * cout * 9 * cin))
         return out
 
+    def pixel_unshuffle(self, image, *, batch: Optional[int] = None, out=None) -> torch.Tensor:
+        """[EXT] ``PixelUnshuffle(8)`` of an fp32 NCHW image (B, C <= 4, H, W), H and W multiples of 8, into fp16 rows ``[batch * (H / 8) * (W / 8)][64 C]``
+        (``pv_pixel_unshuffle8``): column ``c * 64 + i * 8 + j`` of pixel (y, x) is ``image[b][c][8 y + i][8 x + j]``, rounded to fp16 - the first layer of a
+        T2I-Adapter.  ``batch``: the rows' batch; an image of batch 1 is then read for every sample (batch stride 0)."""
+        assert image.dim() == 4 and image.dtype == torch.float32 and image[0].is_contiguous(), (image.shape, image.dtype, image.stride())
+        B, ch, H, W = image.shape
+        batch = B if batch is None else int(batch)
+        assert B in (1, batch), (B, batch)
+        bstride = 0 if (B == 1 and batch > 1) else (image.stride(0) if B > 1 else ch * H * W)
+        rows = batch * (H // 8) * (W // 8)
+        if out is None:
+            out = self.empty((rows, ch * 64))
+        ldo, oc = _rows(out)
+        assert out.dtype == torch.float16 and tuple(out.shape) == (rows, ch * 64) and oc == ch * 64, (out.shape, rows, ch)
+        self.colstats.pop((out.data_ptr(), rows, oc), None)
+        self.keep.extend((image, out))
+        self._add(self.lib.pv_pixel_unshuffle8, _ptr(image), int(bstride), _ptr(out), ldo, batch, ch, H, W,
+                  tag=("pixel_unshuffle8_kernel", 0.0, (4.0 * (1 if bstride == 0 else batch) * ch * H * W) + 2.0 * rows * oc))
+        return out
+
+    def add_feature(self, x, f, *, scale: float = 1.0, scale_tab: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                    colstats: bool = False, out=None) -> torch.Tensor:
+        """[EXT] ``out = x + s * f`` over fp16 rows (``pv_add_feature_rows``; a T2I-Adapter's feature map at the end of a down block), out of place, one fp32
+        fma and one rounding per element.  ``f``: fp16 rows ``[feat_rows][cols]`` with ``feat_rows`` dividing ``x``'s rows - row ``r`` reads ``f[r % feat_rows]``,
+        so a plan at batch 2B or over a sub-batch's row slice reads the per-sample features.  ``s`` = ``scale_tab[state[0]]`` when the fp32 device table (one
+        entry per schedule row) is given with the loop's step counter, else the host ``scale``; where ``s`` is 0 the launch copies ``x``'s bits and never reads
+        ``f``.  ``colstats``: leave the output's per-64-row-block column statistics behind, as ``gemm(colstats=True)`` does, for the GroupNorm that follows."""
+        assert x.dtype == torch.float16 and f.dtype == torch.float16, (x.dtype, f.dtype)
+        ldx, cols = _rows(x)
+        ldf, fc = _rows(f)
+        rows, feat_rows = x.shape[0], f.shape[0]
+        assert fc == cols and feat_rows > 0 and rows % feat_rows == 0, (x.shape, f.shape)
+        assert (scale_tab is None) or (state is not None and scale_tab.dtype == torch.float32 and scale_tab.is_contiguous()), "scale_tab: fp32, with the step counter"
+        if out is None:
+            out = self.empty((rows, cols))
+        ldo, oc = _rows(out)
+        assert out.dtype == torch.float16 and tuple(out.shape) == (rows, cols) and out.data_ptr() not in (x.data_ptr(), f.data_ptr()), (out.shape, rows, cols)
+        cs = None
+        key = (out.data_ptr(), rows, cols)
+        if colstats and ldo == cols and not _NO_COLSTATS:
+            cs = self.colstats[key] = self.empty(((rows + 63) // 64, 2, cols), torch.float32)
+        else:
+            self.colstats.pop(key, None)
+        self.keep.extend(t for t in (x, f, out, scale_tab, state) if t is not None)
+        # one fma per element (+ two for the statistics); bytes: x read, f read (its feat_rows rows from HBM, the repeats from cache), out written, statistics
+        self._add(self.lib.pv_add_feature_rows, _ptr(x), ldx, _ptr(f), ldf, feat_rows, _ptr(out), ldo, rows, cols, float(scale), _ptr(scale_tab),
+                  _ptr(state) if scale_tab is not None else None, _ptr(cs),
+                  tag=("add_feature_rows_kernel", (6.0 if cs is not None else 2.0) * rows * cols,
+                       2.0 * cols * (2 * rows + feat_rows) + (8.0 * ((rows + 63) // 64) * cols if cs is not None else 0.0)))
+        return out
+
     def posterior_sample(self, moments, eps, out=None):
         """moments fp32 [B, 2c, h, w] (mean | logvar), eps fp32 [B, c, h, w] -> mean + exp(0.5 clamp(logvar)) eps."""
         B, c2 = moments.shape[0], moments.shape[1]
