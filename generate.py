@@ -91,6 +91,10 @@ parser.add_argument("--kv_downsample_layers", nargs="+", type=str, default=None,
                     help="Transformers whose keys / values are pooled: name prefixes as --pag_layers takes them, or all (default: the highest-resolution level)")
 parser.add_argument("--hires_kv_downsample", type=int, default=None,
                     help="The factor in the second pass (with --hires_latent_size; default: --kv_downsample, 1 = off in the second pass)")
+parser.add_argument("--vae_tiling", action="store_true",
+                    help="vae.enable_tiling(): decode / encode images larger than one tile in overlapping tiles with blended seams (large --hires_latent_size)")
+parser.add_argument("--vae_tile_size", type=int, default=512, help="tile_sample_min_size of --vae_tiling, in pixels")
+parser.add_argument("--vae_tile_overlap", type=float, default=0.25, help="tile_overlap_factor of --vae_tiling")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -179,6 +183,8 @@ if __name__ == "__main__":
         image_encoder_path=args.image_encoder_path, **cfg)
     for m in (vae, unet, text_encoder, image_encoder, image_adapter, text_adapter):
         m.to(device)
+    if args.vae_tiling:
+        vae.enable_tiling(args.vae_tile_size, args.vae_tile_overlap)
     example = prepare_example(args, tokenizer)
     controlnet, control_image = prepare_control(args, unet)
     with torch.no_grad():

@@ -685,6 +685,26 @@ int32_t pv_add_feature_rows(const void* x, int32_t ldx, const void* f, int32_t l
  * any HIP call. */
 int32_t pv_pixel_unshuffle8(const float* image, int64_t batch_stride, void* out, int32_t ldo, int32_t batch, int32_t channels, int32_t h, int32_t w,
                             void* stream);
+/* (ABI 19, symbol added) [EXT] pv_tile_blend: the seam blend of tiled VAE decode / encode (diffusers' enable_tiling: blend_v, then blend_h, then the crop),
+ * one launch per tile position over the whole batch, bound through _lib.EXT_SIGNATURES.  All operands fp32 NCHW, contiguous:
+ *   tile  [batch][channels][th][tw]        read and written in place        above [batch][channels][ah][tw]   the tile one row up, already blended, or NULL
+ *   out   [batch][channels][out_h][out_w]  written inside the kept region   left  [batch][channels][th][lw]   the tile one column left, likewise
+ * For every pixel (y, x) of every plane, in fp32 (wy = (float)y / ev, wx = (float)x / eh):
+ *   v = tile[y][x]
+ *   if (y < ev)  v = above[ah - ev + y][x] * (1 - wy) + v * wy           the LAST ev rows of the neighbour, whatever its height
+ *   if (x < eh)  v = left[y][lw - eh + x]  * (1 - wx) + v * wx           the LAST eh columns; the vertical blend comes first
+ *   if (y < ev || x < eh)           tile[y][x] = v                       in place: the tiles below and to the right read it
+ *   if (y < keep_h && x < keep_w)   out[oy + y][ox + x] = v              nothing else of out is touched
+ * A lane reads and writes only its own pixels of tile; above and left are read only (they may be one buffer).  16-byte loads and stores where all four
+ * pointers are 16-byte aligned and tw, lw, eh, keep_w, out_w and ox are multiples of 4; a scalar path for everything else - any channel count and extents.
+ * No atomics, no scratch.
+ * tile and out non-null; batch, channels, th, tw, out_h, out_w >= 1; above comes with 1 <= ev <= min(ah, th), no above with ev == 0 (ah is then
+ * ignored); left with 1 <= eh <= min(lw, tw), no left with eh == 0; 1 <= keep_h <= th, 1 <= keep_w <= tw; oy, ox >= 0 and the kept region inside out;
+ * pointers 4-byte aligned; tile and out overlap neither each other nor a neighbour; every operand below 2 GiB.  Anything else returns
+ * hipErrorInvalidValue before any HIP call. */
+int32_t pv_tile_blend(float* tile, const float* above, const float* left, float* out, int32_t batch, int32_t channels, int32_t th, int32_t tw, int32_t ah,
+                      int32_t lw, int32_t ev, int32_t eh, int32_t keep_h, int32_t keep_w, int32_t out_h, int32_t out_w, int32_t oy, int32_t ox,
+                      void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

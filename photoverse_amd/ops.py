@@ -1162,3 +1162,23 @@ class Recorder:
     def step_advance(self, state):
         self.keep.append(state)
         self._add(self.lib.pv_step_advance, _ptr(state))
+
+
+def tile_blend(tile, above, left, out, *, ev: int, eh: int, keep_h: int, keep_w: int, oy: int, ox: int):
+    """[EXT] The seam blend of one tile position of tiled VAE decode / encode (``pv_tile_blend``), launched on the current stream - the tile loop is eager,
+    not a recorded plan.  ``tile`` fp32 (B, C, th, tw), blended IN PLACE: its first ``ev`` rows against the last ``ev`` rows of ``above`` (B, C, ah, tw),
+    then its first ``eh`` columns against the last ``eh`` columns of ``left`` (B, C, th, lw), linear weights ``y / ev`` and ``x / eh``; its top-left
+    ``keep_h x keep_w`` corner then goes to ``out`` (B, C, out_h, out_w) at ``(oy, ox)``.  A neighbour is ``None`` exactly where its extent is 0."""
+    B, ch, th, tw = tile.shape
+    for t, shape in ((tile, None), (above, (B, ch, None, tw)), (left, (B, ch, th, None)), (out, (B, ch, None, None))):
+        if t is None:
+            continue
+        require_cuda(t, "tile_blend operand")
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4, (t.dtype, t.shape, t.stride())
+        assert shape is None or all(w is None or w == g for w, g in zip(shape, t.shape)), (tuple(t.shape), shape)
+    ah = above.shape[2] if above is not None else 0
+    lw = left.shape[3] if left is not None else 0
+    rc = _lib.load().pv_tile_blend(_ptr(tile), _ptr(above), _ptr(left), _ptr(out), B, ch, th, tw, ah, lw, int(ev), int(eh), int(keep_h), int(keep_w),
+                                   out.shape[2], out.shape[3], int(oy), int(ox), torch.cuda.current_stream(tile.device).cuda_stream)
+    if rc != 0:
+        raise HipLaunchError(f"pv_tile_blend failed with hipError {rc}")

@@ -16,6 +16,10 @@ is added after P.V, exact because softmax rows sum to 1).  Images are decoded in
 Downsample2D convs (``F.pad(x,(0,1,0,1))`` + stride 2 / padding 0) are ``pv_gemm_conv`` with ``pad=0``; ``quant_conv`` (1x1, linear)
 is folded into ``conv_out``'s weights in fp32 when the plan is built, and the 8 moment channels come out of one fp32-output GEMM
 whose weight rows are zero-padded to the 128-column tile.
+
+[EXT] ``enable_tiling()`` (diffusers' name): pictures larger than one tile are decoded / encoded tile by tile through the same plans and the seams are
+blended by ``pv_tile_blend`` (``tiling_geometry``, ``tile_grid``, ``AutoencoderKL._tiled``), so neither the attention's score
+matrix nor any activation grows with the picture.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ from typing import Dict
 import torch
 import torch.nn as nn
 
-from .ops import ACT_NONE, ACT_SILU, Recorder, require_cuda
+from .ops import ACT_NONE, ACT_SILU, Recorder, require_cuda, tile_blend
 
 SD15_VAE_CONFIG = dict(latent_channels=4, out_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
                        norm_num_groups=32, scaling_factor=0.18215)
@@ -174,6 +178,8 @@ class AutoencoderKL(nn.Module):
             self.encoder = _Encoder(cfg["in_channels"], cfg["latent_channels"], tuple(cfg["block_out_channels"]),
                                     cfg["layers_per_block"], cfg["norm_num_groups"])
         self._plans: Dict[tuple, object] = {}
+        self.use_tiling = False                  # enable_tiling() / disable_tiling()
+        self.tile_sample_min_size, self.tile_overlap_factor = 512, 0.25
 
     def repack(self):
         self._plans.clear()
@@ -220,9 +226,28 @@ class AutoencoderKL(nn.Module):
         g = rec.groupnorm(x, _f32(m.group_norm.weight), _f32(m.group_norm.bias), batch=b, hw=n, eps=m.group_norm.eps, act=ACT_NONE,
                           groups=self.config.norm_num_groups)
         q = rec.gemm(g, _f16(m.to_q.weight), bias=_f32(m.to_q.bias), rows_per_image=n)    # [b*n, c]
-        k = rec.gemm(g, _f16(m.to_k.weight), bias=_f32(m.to_k.bias), rows_per_image=n)    # contiguous rows: used as a [N][K] weight
         wv = _f16(m.to_v.weight)
         o = rec.empty((b * n, c))
+        if n % 128 and n % 320:
+            # A token count the GEMM tiles do not divide (the edge tiles of tiled decode / encode; n as small as 1): the key axis is padded to npad, a
+            # multiple of 128.  Image i's keys are the rows i*n ... i*n + npad of a buffer with npad zero rows behind the last image - whatever follows
+            # an image's own n keys is finite - and a column bias of -30000 on the padded keys makes their softmax weight exactly 0 (scale * -30000
+            # is below -1300 for every head dim <= 512; fp32 exp underflows to 0 from -104).  V^T comes from the transpose launch, which zero-fills
+            # its padded columns.
+            npad = (n + 127) // 128 * 128
+            kbuf = rec.hold(torch.zeros((b * n + npad, c), dtype=torch.float16, device=rec.device))
+            rec.gemm(g, _f16(m.to_k.weight), bias=_f32(m.to_k.bias), rows_per_image=n, out=kbuf[:b * n])
+            v = rec.gemm(g, wv, rows_per_image=n)                                 # no bias: added after P.V
+            mask = torch.zeros(npad, dtype=torch.float32, device=rec.device)
+            mask[n:] = -30000.0
+            scores = rec.empty((n, npad))
+            for i in range(b):
+                rows = slice(i * n, (i + 1) * n)
+                rec.gemm(q[rows], rec.hold(kbuf[i * n:i * n + npad]), bias=mask, out=scores, splitk=0)
+                rec.softmax_rows(scores, scale=c ** -0.5)
+                rec.gemm(scores, rec.transpose(v[rows], rows_pad=npad), bias=_f32(m.to_v.bias), out=o[rows], splitk=0)
+            return rec.gemm(o, _f16(m.to_out[0].weight), bias=_f32(m.to_out[0].bias), residual=x, rows_per_image=n, colstats=True)
+        k = rec.gemm(g, _f16(m.to_k.weight), bias=_f32(m.to_k.bias), rows_per_image=n)    # contiguous rows: used as a [N][K] weight
         scores = rec.empty((n, n))                                            # reused by every image (launches are stream ordered)
         vt = rec.empty((c, n))
         for i in range(b):
@@ -305,13 +330,10 @@ class AutoencoderKL(nn.Module):
         worst = max(boc[0] * H * W * 2, 64 * H * W * 2)      # first-level activations / the im2col rows of conv_in
         return max(1, min(batch, self.MAX_OPERAND_BYTES // worst))
 
-    def encode(self, x: torch.Tensor):
-        """``x``: (B,3,H,W) pixels in [-1,1] on the GPU -> ``.latent_dist`` over (B,latent_channels,H/8,W/8), fp32."""
-        if not self.config.with_encoder:
-            raise RuntimeError("this AutoencoderKL was built with with_encoder=False")
-        require_cuda(x, "pixel_values")
+    def _encode_moments(self, x: torch.Tensor) -> torch.Tensor:
+        """The encoder plan over ``x`` (N,3,H,W) in sub-batches -> the moments (N,2*latent_channels,H/down,W/down), fp32."""
         B, _, H, W = x.shape
-        down = 2 ** (len(self.config.block_out_channels) - 1)
+        down = self._up
         assert H % down == 0 and W % down == 0, (H, W, down)
         sb = self._sub_batch_encode(B, H, W)
         key = ("enc", sb, H, W, x.device)
@@ -326,10 +348,10 @@ class AutoencoderKL(nn.Module):
             plan.rec.run()
             m = plan.moments.view(sb, plan.h, plan.w, -1)[:n, :, :, :plan.nm]
             outs.append(m.permute(0, 3, 1, 2).contiguous())
-        return SimpleNamespace(latent_dist=DiagonalGaussianDistribution(torch.cat(outs, 0)))
+        return torch.cat(outs, 0)
 
-    def decode(self, z: torch.Tensor):
-        require_cuda(z, "latents")
+    def _decode_images(self, z: torch.Tensor) -> torch.Tensor:
+        """The decoder plan over ``z`` (N,latent_channels,h,w) in sub-batches -> the images (N,3,h*up,w*up), fp32."""
         B, _, h, w = z.shape
         sb = self._sub_batch(B, h, w)
         key = (sb, h, w, z.device)
@@ -343,4 +365,113 @@ class AutoencoderKL(nn.Module):
             plan.z[:n].copy_(chunk)
             plan.rec.run()
             outs.append(plan.img[:n].clone())
-        return SimpleNamespace(sample=torch.cat(outs, 0).to(z.dtype))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    def encode(self, x: torch.Tensor):
+        """``x``: (B,3,H,W) pixels in [-1,1] on the GPU -> ``.latent_dist`` over (B,latent_channels,H/8,W/8), fp32.  With tiling enabled an image larger
+        than one tile in either dimension goes through ``tiled_encode``."""
+        if not self.config.with_encoder:
+            raise RuntimeError("this AutoencoderKL was built with with_encoder=False")
+        require_cuda(x, "pixel_values")
+        if self.use_tiling and max(x.shape[2:]) > self.tile_sample_min_size:
+            return self.tiled_encode(x)
+        return SimpleNamespace(latent_dist=DiagonalGaussianDistribution(self._encode_moments(x)))
+
+    def decode(self, z: torch.Tensor):
+        """With tiling enabled a latent larger than one tile in either dimension goes through ``tiled_decode``."""
+        require_cuda(z, "latents")
+        if self.use_tiling and max(z.shape[2:]) > self.tile_sample_min_size // self._up:
+            return self.tiled_decode(z)
+        return SimpleNamespace(sample=self._decode_images(z).to(z.dtype))
+
+    # ------------------------------------------------------------------ tiling
+    @property
+    def _up(self) -> int:
+        return 2 ** (len(self.config.block_out_channels) - 1)
+
+    def enable_tiling(self, tile_sample_min_size: int = 512, tile_overlap_factor: float = 0.25):
+        """[EXT] diffusers' ``vae.enable_tiling()``: ``decode`` / ``encode`` of anything larger than one tile run tile by tile and blend the seams
+        (``tiled_decode`` / ``tiled_encode``), so no plan sees more than ``tile_sample_min_size`` pixels a side.  Raises ``ValueError`` on parameters
+        that ``tiling_geometry`` rejects; smaller inputs keep the untiled path and its bits."""
+        tiling_geometry(tile_sample_min_size, tile_overlap_factor, self._up)
+        self.tile_sample_min_size, self.tile_overlap_factor = int(tile_sample_min_size), float(tile_overlap_factor)
+        self.use_tiling = True
+
+    def disable_tiling(self):
+        self.use_tiling = False
+
+    def _tiled(self, x, geo, run, channels):
+        """The tile loop both directions share.  ``geo``: one direction of ``tiling_geometry`` (tile / stride in input units, blend / keep in output
+        units, output = input * num // den); ``run``: equal-shaped input tiles (N,C,th,tw) -> their fp32 NCHW results through the cached plans.
+        The tiles of one tile row that have the same shape - all images, all positions - are one ``run`` (sub-batched by the plan as ever).  Each
+        tile is then blended in raster order by one ``pv_tile_blend`` launch, which also writes its kept region to the output.  Two tile rows of
+        results are alive at any time: the row being blended and the one above it."""
+        B, _, H, W = x.shape
+        sc = lambda n: n * geo.num // geo.den
+        rows, cols = tile_grid(H, geo.tile, geo.stride), tile_grid(W, geo.tile, geo.stride)
+        out = torch.empty((B, channels, sc(H), sc(W)), dtype=torch.float32, device=x.device)
+        prev = None
+        for i, (y0, th) in enumerate(rows):
+            by_width: Dict[int, list] = {}
+            for j, (_, tw) in enumerate(cols):
+                by_width.setdefault(tw, []).append(j)
+            cur = [None] * len(cols)
+            for tw, js in by_width.items():
+                res = run(torch.cat([x[:, :, y0:y0 + th, cols[j][0]:cols[j][0] + tw] for j in js], 0))       # position-major: B images per position
+                for k, j in enumerate(js):
+                    cur[j] = res[k * B:(k + 1) * B]
+            for j, tile in enumerate(cur):
+                above, left = (prev[j] if i else None), (cur[j - 1] if j else None)
+                ev = min(above.shape[2], tile.shape[2], geo.blend) if i else 0
+                eh = min(left.shape[3], tile.shape[3], geo.blend) if j else 0
+                tile_blend(tile, above if ev else None, left if eh else None, out, ev=ev, eh=eh, keep_h=min(geo.keep, tile.shape[2]),
+                           keep_w=min(geo.keep, tile.shape[3]), oy=i * geo.keep, ox=j * geo.keep)
+            prev = cur
+        return out
+
+    def tiled_decode(self, z: torch.Tensor):
+        """[EXT] diffusers' ``tiled_decode``, always tiled (``decode`` dispatches here): latent tiles of ``tile_sample_min_size / up`` a side at stride
+        ``int(t * (1 - f))`` through the decoder plan, seams blended over ``int(T * f)`` pixels, vertical first."""
+        require_cuda(z, "latents")
+        geo = tiling_geometry(self.tile_sample_min_size, self.tile_overlap_factor, self._up).decode
+        return SimpleNamespace(sample=self._tiled(z, geo, self._decode_images, self.config.out_channels).to(z.dtype))
+
+    def tiled_encode(self, x: torch.Tensor):
+        """[EXT] diffusers' ``tiled_encode``, always tiled: pixel tiles of ``tile_sample_min_size`` a side at stride ``int(T * (1 - f))`` through the
+        encoder plan, the moments blended over ``int(t * f)`` latents."""
+        if not self.config.with_encoder:
+            raise RuntimeError("this AutoencoderKL was built with with_encoder=False")
+        require_cuda(x, "pixel_values")
+        up = self._up
+        assert x.shape[2] % up == 0 and x.shape[3] % up == 0, (tuple(x.shape), up)
+        geo = tiling_geometry(self.tile_sample_min_size, self.tile_overlap_factor, up).encode
+        return SimpleNamespace(latent_dist=DiagonalGaussianDistribution(self._tiled(x, geo, self._encode_moments, 2 * self.config.latent_channels)))
+
+
+def tiling_geometry(tile_sample_min_size, tile_overlap_factor, up: int):
+    """The integers of tiled decode and encode for pixel tile ``T``, overlap ``f`` and the VAE's scale ``up`` (pure host arithmetic, diffusers' own):
+    ``.decode`` - latent tile ``t = T // up``, stride ``int(t * (1 - f))`` latents, blend ``int(T * f)`` and keep ``T - blend`` pixels; ``.encode`` - tile
+    ``T``, stride ``int(T * (1 - f))`` pixels, blend ``int(t * f)`` and keep ``t - blend`` latents.  ``ValueError`` unless ``T`` is a positive multiple
+    of ``up``, ``0 <= f < 1``, both strides are at least 1 and, in both directions, the kept extent is exactly the stride on the output grid - otherwise
+    the kept regions would not meet the tiles they were cut from."""
+    T, f = tile_sample_min_size, tile_overlap_factor
+    if isinstance(T, bool) or not isinstance(T, int) or T <= 0 or T % up:
+        raise ValueError(f"tile_sample_min_size must be a positive multiple of {up} (the VAE's scale factor), got {T!r}")
+    if isinstance(f, bool) or not isinstance(f, (int, float)) or not 0 <= f < 1:
+        raise ValueError(f"tile_overlap_factor must be a number in [0, 1), got {f!r}")
+    t = T // up
+    dec = SimpleNamespace(tile=t, stride=int(t * (1 - f)), blend=int(T * f), keep=T - int(T * f), num=up, den=1)
+    enc = SimpleNamespace(tile=T, stride=int(T * (1 - f)), blend=int(t * f), keep=t - int(t * f), num=1, den=up)
+    if dec.stride < 1 or enc.stride < 1:
+        raise ValueError(f"tile_overlap_factor {f} leaves no stride between tiles of tile_sample_min_size {T} ({t} latents)")
+    if dec.keep != dec.stride * up or enc.keep * up != enc.stride:
+        raise ValueError(f"tile_sample_min_size {T} and tile_overlap_factor {f} do not agree on the tile grid: decode keeps {dec.keep} pixels of a "
+                         f"tile at stride {dec.stride} x {up}, encode {enc.keep} latents at stride {enc.stride} / {up}; choose them so that "
+                         f"tile_sample_min_size * tile_overlap_factor is a multiple of {up}")
+    return SimpleNamespace(decode=dec, encode=enc)
+
+
+def tile_grid(size: int, tile: int, stride: int):
+    """``[(start, extent)]`` of the tiles along one axis: starts ``0, stride, ...`` below ``size``, extents clipped at the border (the last ones may be
+    as small as 1).  Tile ``i`` owns ``min(stride, extent)`` of the axis from its start: together exactly ``[0, size)``."""
+    return [(s, min(tile, size - s)) for s in range(0, size, stride)]
