@@ -95,6 +95,8 @@ parser.add_argument("--vae_tiling", action="store_true",
                     help="vae.enable_tiling(): decode / encode images larger than one tile in overlapping tiles with blended seams (large --hires_latent_size)")
 parser.add_argument("--vae_tile_size", type=int, default=512, help="tile_sample_min_size of --vae_tiling, in pixels")
 parser.add_argument("--vae_tile_overlap", type=float, default=0.25, help="tile_overlap_factor of --vae_tiling")
+parser.add_argument("--vae_flash_attention", action="store_true",
+                    help="vae.enable_flash_attention(): the VAE mid-block attention as one flash launch with no score matrix (untiled decode of large latents)")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -164,6 +166,15 @@ def prepare_control(args, unet):
     return cn.to(unet.device), image.clamp(0, 1).contiguous()
 
 
+def configure_vae(args, vae):
+    """The VAE switches of the command line (--vae_tiling, --vae_flash_attention): the VAE object carries them into run_inference."""
+    if args.vae_tiling:
+        vae.enable_tiling(args.vae_tile_size, args.vae_tile_overlap)
+    if args.vae_flash_attention:
+        vae.enable_flash_attention()
+    return vae
+
+
 if __name__ == "__main__":
     args = parser.parse_args()
     if not torch.cuda.is_available():
@@ -183,8 +194,7 @@ if __name__ == "__main__":
         image_encoder_path=args.image_encoder_path, **cfg)
     for m in (vae, unet, text_encoder, image_encoder, image_adapter, text_adapter):
         m.to(device)
-    if args.vae_tiling:
-        vae.enable_tiling(args.vae_tile_size, args.vae_tile_overlap)
+    configure_vae(args, vae)
     example = prepare_example(args, tokenizer)
     controlnet, control_image = prepare_control(args, unet)
     with torch.no_grad():

@@ -705,6 +705,20 @@ int32_t pv_pixel_unshuffle8(const float* image, int64_t batch_stride, void* out,
 int32_t pv_tile_blend(float* tile, const float* above, const float* left, float* out, int32_t batch, int32_t channels, int32_t th, int32_t tw, int32_t ah,
                       int32_t lw, int32_t ev, int32_t eh, int32_t keep_h, int32_t keep_w, int32_t out_h, int32_t out_w, int32_t oy, int32_t ox,
                       void* stream);
+/* (ABI 19, symbol added) [EXT] pv_vae_attention: the VAE mid block's single-head attention (head width 256 / 512) as ONE flash launch over the whole
+ * sub-batch (AutoencoderKL.enable_flash_attention; pv_vaeattn.hip), bound through _lib.EXT_SIGNATURES.  No [n][n] score matrix exists anywhere.
+ *   out = softmax(scale * q k^T) v   per image: image i owns the rows i*n ... i*n + n - 1 of every operand and attends only to its own rows
+ * q, k, v: fp16 rows [batch*n][d] with the leading dimensions ldq, ldk, ldv (column slices of one fused QKV buffer will do); out: fp16 [batch*n][d],
+ * leading dimension ldo.  Scores, the running maximum and the denominator are fp32 (online softmax, base-2 exponent with scale * log2 e folded into the
+ * fp32 score); P is rounded to fp16 once, for the P.V MFMA, and the denominator is the sum of those ROUNDED values, so numerator and denominator agree;
+ * accumulation and the final division are fp32, one rounding to fp16.
+ * d in {256, 512}; batch >= 1; any n >= 1.  Keys beyond an image's n contribute exactly 0 and are never loaded (the row behind an image may be another
+ * image's or hold NaN: no 0 * x); query rows beyond n are not stored; nothing outside out[r][0..d), r < batch*n, is written.  No scratch buffer, no atomics,
+ * a fixed summation order: every launch gives the same bits, and a batch equals its images launched one by one.  Safe under stream capture.
+ * Returns hipErrorInvalidValue before any HIP call for: a null pointer; d outside the set; an ld below d or not a multiple of 8; a pointer not 16-byte
+ * aligned; batch or n below 1; a non-finite scale; out overlapping an input; any operand extent ((batch*n - 1) * ld + d halfs) of 2 GiB or more. */
+int32_t pv_vae_attention(const void* q, const void* k, const void* v, int32_t ldq, int32_t ldk, int32_t ldv, void* out, int32_t ldo, int32_t batch,
+                         int32_t n, int32_t d, float scale, void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

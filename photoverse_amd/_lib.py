@@ -198,6 +198,8 @@ EXT_SIGNATURES = {
     "pv_pixel_unshuffle8": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     # the seam blend of tiled VAE decode / encode (``tests/test_vae_tiling_gpu.py``)
     "pv_tile_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 14 + [c_void_p]),
+    # the VAE mid block's attention as one flash launch (``tests/test_vae_flash_gpu.py``)
+    "pv_vae_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
 }
 
 #: ``mode`` of ``pv_token_pool`` (the header's PV_POOL_*)

@@ -867,6 +867,29 @@ class Recorder:
                   tag=("token_pool_kernel", (1.0 * batch * h * w * cols + batch * hp * wp * cols) if method == "avg" else 0.0, 2.0 * cols * (rd + batch * hp * wp)))
         return out
 
+    def vae_attention(self, q, k, v, out=None, *, batch: int, n: int, scale: float) -> torch.Tensor:
+        """[EXT] ``softmax(scale * q k^T) v`` per image as ONE flash launch (``pv_vae_attention``; the VAE mid block's single wide head, ``d`` in {256, 512}):
+        ``q`` / ``k`` / ``v`` are fp16 2-D row views ``[batch * n][d]`` - column slices of one fused QKV buffer will do - image ``i`` owns the rows
+        ``i * n ... i * n + n - 1`` and attends only to them; any ``n >= 1``.  -> fp16 ``[batch * n][d]``.  No score matrix is allocated."""
+        for t in (q, k, v):
+            assert t.dtype == torch.float16 and t.shape[0] == batch * n, (t.shape, t.dtype, batch, n)
+        ldq, d = _rows(q)
+        ldk, dk = _rows(k)
+        ldv, dv = _rows(v)
+        assert dk == d and dv == d, (d, dk, dv)
+        if d not in (256, 512):
+            raise ValueError(f"vae_attention: the head width must be 256 or 512, got {d}")
+        if out is None:
+            out = self.empty((batch * n, d))
+        ldo, do = _rows(out)
+        assert out.dtype == torch.float16 and tuple(out.shape) == (batch * n, d) and do == d, (out.shape, batch, n, d)
+        self.colstats.pop((out.data_ptr(), out.shape[0], d), None)
+        self.keep.extend((q, k, v, out))
+        # flops: the two products; bytes: q read and out written once, k and v once per image (their re-reads by the query tiles come from L2 / MALL)
+        self._add(self.lib.pv_vae_attention, _ptr(q), _ptr(k), _ptr(v), ldq, ldk, ldv, _ptr(out), ldo, batch, n, d, float(scale),
+                  tag=(f"vae_attn_kernel<{d}>", 4.0 * batch * n * n * d, 2.0 * 4 * batch * n * d))
+        return out
+
     def attn_colmass(self, q, k, *, batch: int, heads: int, nq: int, nk: int, d: int, out=None) -> torch.Tensor:
         """[EXT] The attention each key receives (``pv_attn_colmass``; self-attention guidance): ``mass[b][j] = mean_heads sum_i softmax_j(q_i . k_j / sqrt d)``
         -> fp32 ``[batch][nk]``, every row summing to ``nq``.  ``q`` / ``k``: the fp16 row views ``attention`` takes - ``[batch * nq][heads * d]`` and

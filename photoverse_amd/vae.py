@@ -9,9 +9,9 @@ Parameter names follow diffusers (``post_quant_conv``, ``decoder.conv_in``, ``de
 ``encoder.down_blocks.i.{resnets.j,downsamplers.0.conv}``, ``encoder.mid_block``, ``encoder.conv_norm_out``, ``encoder.conv_out``)
 so the HF ``vae`` checkpoint loads.  Everything runs on the UNet's kernels:
 3x3 convs = implicit-GEMM ``pv_gemm_conv`` (nearest-x2 upsample folded into the gather), GroupNorm(+SiLU) kernels, and the
-mid block's single-head attention over the H*W tokens (head dim 512, too wide for the flash kernel's register tiles) as
-GEMM (Q.K^T per image) -> ``pv_softmax_rows`` -> GEMM (P.V with V^T produced directly by an operand-swapped GEMM; the V bias
-is added after P.V, exact because softmax rows sum to 1).  Images are decoded in sub-batches so that no operand exceeds the
+mid block's single-head attention over the H*W tokens (head dim 512).  By default - the form that came first, when no flash kernel
+had register tiles that wide - it is GEMM (Q.K^T per image) -> ``pv_softmax_rows`` -> GEMM (P.V with V^T produced directly by an
+operand-swapped GEMM; the V bias is added after P.V, exact because softmax rows sum to 1) through an fp16 ``[n][n]`` score buffer.  Images are decoded in sub-batches so that no operand exceeds the
 2 GiB the buffer descriptors address.  Encoder specifics: ``conv_in`` (3 channels) is im2col + GEMM like the decoder's; the
 Downsample2D convs (``F.pad(x,(0,1,0,1))`` + stride 2 / padding 0) are ``pv_gemm_conv`` with ``pad=0``; ``quant_conv`` (1x1, linear)
 is folded into ``conv_out``'s weights in fp32 when the plan is built, and the 8 moment channels come out of one fp32-output GEMM
@@ -20,6 +20,11 @@ whose weight rows are zero-padded to the 128-column tile.
 [EXT] ``enable_tiling()`` (diffusers' name): pictures larger than one tile are decoded / encoded tile by tile through the same plans and the seams are
 blended by ``pv_tile_blend`` (``tiling_geometry``, ``tile_grid``, ``AutoencoderKL._tiled``), so neither the attention's score
 matrix nor any activation grows with the picture.
+
+[EXT] ``enable_flash_attention()`` (what diffusers users switch on as ``enable_xformers_memory_efficient_attention`` / the SDPA processor): the mid-block
+attention of decoder and encoder becomes GroupNorm -> ONE fused QKV GEMM -> ONE ``pv_vae_attention`` launch over the whole sub-batch (``pv_vaeattn.hip``:
+online softmax, fp32 scores, no score matrix) -> ``to_out`` - four launches whatever the batch and for every token count, so an untiled decode no longer
+stops where the ``[n][n]`` buffer passes 2 GiB.  Off by default: the plans, launches and bits are then exactly the ones above.  Composes with tiling.
 """
 from __future__ import annotations
 
@@ -179,6 +184,7 @@ class AutoencoderKL(nn.Module):
                                     cfg["layers_per_block"], cfg["norm_num_groups"])
         self._plans: Dict[tuple, object] = {}
         self.use_tiling = False                  # enable_tiling() / disable_tiling()
+        self.use_flash_attention = False         # enable_flash_attention() / disable_flash_attention()
         self.tile_sample_min_size, self.tile_overlap_factor = 512, 0.25
 
     def repack(self):
@@ -225,6 +231,14 @@ class AutoencoderKL(nn.Module):
         n, c = h * w, m.to_q.in_features
         g = rec.groupnorm(x, _f32(m.group_norm.weight), _f32(m.group_norm.bias), batch=b, hw=n, eps=m.group_norm.eps, act=ACT_NONE,
                           groups=self.config.norm_num_groups)
+        if self.use_flash_attention:
+            # four launches for any b and any n: the fused [3c][c] projection (the V bias goes straight into V), one flash launch over the three column
+            # slices of its output - every image attends to its own n rows, nothing is padded - and to_out
+            wqkv = torch.cat([_f16(m.to_q.weight), _f16(m.to_k.weight), _f16(m.to_v.weight)], 0).contiguous()
+            bqkv = torch.cat([_f32(m.to_q.bias), _f32(m.to_k.bias), _f32(m.to_v.bias)], 0).contiguous()
+            qkv = rec.gemm(g, wqkv, bias=bqkv, rows_per_image=n)                                  # [b*n, 3c]
+            o = rec.vae_attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], batch=b, n=n, scale=c ** -0.5)
+            return rec.gemm(o, _f16(m.to_out[0].weight), bias=_f32(m.to_out[0].bias), residual=x, rows_per_image=n, colstats=True)
         q = rec.gemm(g, _f16(m.to_q.weight), bias=_f32(m.to_q.bias), rows_per_image=n)    # [b*n, c]
         wv = _f16(m.to_v.weight)
         o = rec.empty((b * n, c))
@@ -336,7 +350,7 @@ class AutoencoderKL(nn.Module):
         down = self._up
         assert H % down == 0 and W % down == 0, (H, W, down)
         sb = self._sub_batch_encode(B, H, W)
-        key = ("enc", sb, H, W, x.device)
+        key = self._plan_key("enc", sb, H, W, x.device)
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = self._plan_encode(sb, H, W, x.device)
@@ -354,7 +368,7 @@ class AutoencoderKL(nn.Module):
         """The decoder plan over ``z`` (N,latent_channels,h,w) in sub-batches -> the images (N,3,h*up,w*up), fp32."""
         B, _, h, w = z.shape
         sb = self._sub_batch(B, h, w)
-        key = (sb, h, w, z.device)
+        key = self._plan_key("dec", sb, h, w, z.device)
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = self._plan(sb, h, w, z.device)
@@ -366,6 +380,11 @@ class AutoencoderKL(nn.Module):
             plan.rec.run()
             outs.append(plan.img[:n].clone())
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    def _plan_key(self, kind, sb, h, w, dev):
+        """The cache key of a decoder (``kind == "dec"``) or encoder plan: the attention form is part of it, so toggling ``use_flash_attention`` never
+        replays the other form's plan."""
+        return ((sb, h, w, dev) if kind == "dec" else ("enc", sb, h, w, dev)) + (bool(self.use_flash_attention),)
 
     def encode(self, x: torch.Tensor):
         """``x``: (B,3,H,W) pixels in [-1,1] on the GPU -> ``.latent_dist`` over (B,latent_channels,H/8,W/8), fp32.  With tiling enabled an image larger
@@ -399,6 +418,18 @@ class AutoencoderKL(nn.Module):
 
     def disable_tiling(self):
         self.use_tiling = False
+
+    def enable_flash_attention(self):
+        """[EXT] The mid-block attention of decoder and encoder as one ``pv_vae_attention`` launch behind one fused QKV GEMM (module docstring; DESIGN.md
+        section 5) - the switch diffusers users know as memory-efficient attention.  Raises ``ValueError`` unless the mid-block width (the kernel's head
+        width) is 256 or 512.  Plans recorded with the switch off stay cached and come back, bit for bit, with ``disable_flash_attention()``."""
+        c = self.decoder.mid_block.attentions[0].to_q.in_features
+        if c not in (256, 512):
+            raise ValueError(f"enable_flash_attention: pv_vae_attention has head widths 256 and 512, this VAE's mid block is {c} wide")
+        self.use_flash_attention = True
+
+    def disable_flash_attention(self):
+        self.use_flash_attention = False
 
     def _tiled(self, x, geo, run, channels):
         """The tile loop both directions share.  ``geo``: one direction of ``tiling_geometry`` (tile / stride in input units, blend / keep in output
