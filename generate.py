@@ -97,6 +97,8 @@ parser.add_argument("--vae_tile_size", type=int, default=512, help="tile_sample_
 parser.add_argument("--vae_tile_overlap", type=float, default=0.25, help="tile_overlap_factor of --vae_tiling")
 parser.add_argument("--vae_flash_attention", action="store_true",
                     help="vae.enable_flash_attention(): the VAE mid-block attention as one flash launch with no score matrix (untiled decode of large latents)")
+parser.add_argument("--vae_tiny_path", type=str, default=None,
+                    help="AutoencoderTiny (TAESD) directory, or 'random' for seeded random weights: the tiny autoencoder replaces the VAE in run_inference")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -175,6 +177,30 @@ def configure_vae(args, vae):
     return vae
 
 
+def prepare_vae_tiny(args, device):
+    """``--vae_tiny_path`` -> an ``AutoencoderTiny`` on ``device`` (the ``vae`` of ``run_inference``), or None.  ``--vae_tiling`` and
+    ``--vae_flash_attention`` are switches of ``AutoencoderKL``: combining them with it exits."""
+    if args.vae_tiny_path is None:
+        return None
+    for flag in ("vae_tiling", "vae_flash_attention"):
+        if getattr(args, flag):
+            raise SystemExit(f"--{flag} is a switch of AutoencoderKL: it does not combine with --vae_tiny_path (AutoencoderTiny has no attention and is not tiled)")
+    from photoverse_amd.vae_tiny import AutoencoderTiny
+    if args.vae_tiny_path == "random":
+        with torch.random.fork_rng(devices=[]):                   # the generation's own random stream stays what it is without the flag
+            torch.manual_seed(0 if args.seed is None else args.seed)
+            vae = AutoencoderTiny()
+    else:
+        vae = AutoencoderTiny.from_pretrained(args.vae_tiny_path)
+    return vae.requires_grad_(False).to(device)
+
+
+def select_vae(args, vae, device):
+    """The object ``run_inference`` gets as its ``vae``: the tiny autoencoder of ``--vae_tiny_path``, else the loaded ``AutoencoderKL`` with its switches."""
+    tiny = prepare_vae_tiny(args, device)
+    return configure_vae(args, vae) if tiny is None else tiny
+
+
 if __name__ == "__main__":
     args = parser.parse_args()
     if not torch.cuda.is_available():
@@ -194,7 +220,7 @@ if __name__ == "__main__":
         image_encoder_path=args.image_encoder_path, **cfg)
     for m in (vae, unet, text_encoder, image_encoder, image_adapter, text_adapter):
         m.to(device)
-    configure_vae(args, vae)
+    vae = select_vae(args, vae, device)
     example = prepare_example(args, tokenizer)
     controlnet, control_image = prepare_control(args, unet)
     with torch.no_grad():

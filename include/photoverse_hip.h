@@ -30,7 +30,8 @@ extern "C" {
 
 #define PV_ABI_VERSION 19
 
-enum pv_act { PV_ACT_NONE = 0, PV_ACT_SILU = 1, PV_ACT_QUICK_GELU = 2, PV_ACT_LEAKY_RELU = 3, PV_ACT_GELU = 4 };
+enum pv_act { PV_ACT_NONE = 0, PV_ACT_SILU = 1, PV_ACT_QUICK_GELU = 2, PV_ACT_LEAKY_RELU = 3, PV_ACT_GELU = 4,
+              PV_ACT_RELU = 5 /* pv_tiny_conv3x3 only: every other launcher rejects it */ };
 
 int pv_abi_version(void);
 /* number of HIP devices visible, or -1 on runtime error; never initialises a context */
@@ -719,6 +720,32 @@ int32_t pv_tile_blend(float* tile, const float* above, const float* left, float*
  * aligned; batch or n below 1; a non-finite scale; out overlapping an input; any operand extent ((batch*n - 1) * ld + d halfs) of 2 GiB or more. */
 int32_t pv_vae_attention(const void* q, const void* k, const void* v, int32_t ldq, int32_t ldk, int32_t ldv, void* out, int32_t ldo, int32_t batch,
                          int32_t n, int32_t d, float scale, void* stream);
+/* (ABI 19, symbol added) [EXT] pv_tiny_conv3x3: the 3x3 convs (pad 1) of AutoencoderTiny / TAESD (pv_tinyconv.hip), bound through _lib.EXT_SIGNATURES.
+ *   y[b][oy][ox][co] = bias[co] (0 if bias == NULL)
+ *                    + sum_{ky,kx,ci} X[b][iy][ix][ci] * w[co][(ky*3 + kx)*cin + ci]        w: fp16 [cout][9*cin], tap-major (as pv_hint_conv3x3)
+ *                    + res[row][co]                                                         optional fp16 rows (leading dimension ldr), added in fp32
+ *   out = act(y)                                                                            act = PV_ACT_NONE or PV_ACT_RELU
+ * fp32 accumulation in a fixed order.  (iy, ix) = (oy*stride + ky - 1, ox*stride + kx - 1); taps outside the (virtual) input are 0.
+ * Input forms:   x_is_image = 0   fp16 rows [batch*h*wd][64], leading dimension ldx; cin == 64; pre == PV_TINY_PRE_NONE.
+ *                x_is_image = 1   fp32 NCHW [batch][cin][h][wd], contiguous, cin <= 4, read through pre: NONE, TANH3 (3*tanh(x/3)) or UNIT ((x + 1)/2); the
+ *                                 padding taps are 0 AFTER pre.  stride 1, no upsample, ldx ignored.  Ordinary vector instructions (K <= 36).
+ * Geometry (rows input): stride 1 or 2, ho = (h' - 1)/stride + 1, wo likewise; upsample 0 or 1: with 1 the conv sees the 2h x 2wd nearest-neighbour
+ *                upsampling (h' = 2h) - tap (iy, ix) reads row (iy >> 1, ix >> 1), the zero padding lies outside [0, 2h) x [0, 2wd), and the upsampled tensor
+ *                is never written.  stride 2 with upsample 1 is rejected.
+ * Output forms:  out_is_image = 0  fp16 rows [batch*ho*wo][64], leading dimension ldo; cout == 64; ONE rounding, after residual and activation; ReLU gives
+ *                                  +0 for every y <= 0 (no negative zero).
+ *                out_is_image = 1  fp32 NCHW [batch][cout][ho][wo], cout <= 4, holding out_scale*y + out_shift (one fma); no fp16 rounding; act must be
+ *                                  NONE and res NULL.  Image in with image out is rejected.
+ * Inputs are read only; out overlaps nothing the launch reads.  No atomics, no scratch buffer; every launch gives the same bits, and a batch gives the bits
+ * of its images launched one by one (no tap crosses into a neighbouring image's rows; rows behind the last image and columns beyond the width are never
+ * read).  Safe under stream capture.  Pointers 16-byte aligned; ldx, ldo, ldr multiples of 8 and >= the width; every extent below 2 GiB; batch, h, wd >= 1;
+ * out_scale, out_shift finite.  Anything else returns hipErrorInvalidValue before any HIP call. */
+#define PV_TINY_PRE_NONE 0
+#define PV_TINY_PRE_TANH3 1
+#define PV_TINY_PRE_UNIT 2
+int32_t pv_tiny_conv3x3(const void* x, int32_t x_is_image, int32_t ldx, int32_t pre, const void* w, const float* bias, const void* res, int32_t ldr,
+                        void* out, int32_t out_is_image, int32_t ldo, float out_scale, float out_shift, int32_t batch, int32_t cin, int32_t cout, int32_t h,
+                        int32_t wd, int32_t stride, int32_t upsample, int32_t act, void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

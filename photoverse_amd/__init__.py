@@ -4,3 +4,10 @@ Python host layer over ``libphotoverse_hip.so`` (hand-written HIP kernels, C-ABI
 There is no CPU or eager fallback: ops raise if the library or a HIP device is missing.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):           # lazy: importing the package stays free of torch
+    if name == "AutoencoderTiny":
+        from .vae_tiny import AutoencoderTiny
+        return AutoencoderTiny
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -200,6 +200,8 @@ EXT_SIGNATURES = {
     "pv_tile_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 14 + [c_void_p]),
     # the VAE mid block's attention as one flash launch (``tests/test_vae_flash_gpu.py``)
     "pv_vae_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    # the 3x3 convs of AutoencoderTiny (``tests/test_vae_tiny_gpu.py``)
+    "pv_tiny_conv3x3": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float] + [c_int] * 8 + [c_void_p]),
 }
 
 #: ``mode`` of ``pv_token_pool`` (the header's PV_POOL_*)

@@ -21,6 +21,9 @@ from ._lib import (AttnBwdParams, AttnParams, GemmParams, GroupNormBwdParams, Gr
                    XAttnBwdParams, XAttnFusedParams, XAttnLnqParams, XAttnParams)
 
 ACT_NONE, ACT_SILU, ACT_QUICK_GELU, ACT_LEAKY_RELU, ACT_GELU = 0, 1, 2, 3, 4
+ACT_RELU = 5                     # pv_tiny_conv3x3 only
+#: ``pre`` of ``Recorder.tiny_conv`` (the header's PV_TINY_PRE_*)
+TINY_PRE = {None: 0, "none": 0, "tanh3": 1, "unit": 2}
 
 import os as _os
 #: split-K heuristic: split until about SPLITK_TARGET workgroups exist (2 per CU), at most SPLITK_MAX ways
@@ -947,6 +950,54 @@ class Recorder:
         self._add(self.lib.pv_hint_conv3x3, _ptr(x), int(image), ldx, _ptr(w), _ptr(bias), _ptr(out), ldo, batch, cin, cout, h, wd, int(stride), int(act),
                   tag=("hint_conv_image_kernel" if image else "hint_conv_rows_kernel", 2.0 * m * cout * 9 * cin,
                        (4.0 if image else 2.0) * batch * h * wd * cin + 2.0 * m * cout + 2.0 * cout * 9 * cin))
+        return out
+
+    def tiny_conv(self, x, w, bias=None, *, batch: int, h: int, wd: int, stride: int = 1, upsample: bool = False, act: int = ACT_NONE, residual=None,
+                  pre: Optional[str] = None, image_out: bool = False, out_scale: float = 1.0, out_shift: float = 0.0, out=None):
+        """[EXT] One 3x3 conv (pad 1) of ``AutoencoderTiny`` (``pv_tiny_conv3x3``).  ``x``: fp16 rows ``[batch * h * wd][64]`` (a 2-D row view), or the fp32
+        NCHW image ``(batch, cin <= 4, h, wd)`` read through ``pre`` (None, ``"tanh3"``: ``3 tanh(x / 3)``, ``"unit"``: ``(x + 1) / 2``; zero padding after
+        it).  ``w``: fp16 ``[cout][9 * cin]``, tap-major; ``bias``: fp32 ``[cout]`` or None.  Rows input only: ``stride`` 1 / 2, or ``upsample`` - the conv
+        of the nearest-x2 upsampled input, which is never written.  -> fp16 rows ``[batch * ho * wo][64]`` = ``act(conv + bias + residual)`` (``act``
+        ACT_NONE / ACT_RELU, ``residual`` fp16 rows), or with ``image_out`` the fp32 NCHW image ``(batch, cout <= 4, ho, wo)`` = ``out_scale * conv +
+        out_shift``.  ``out=``: a buffer of that form to write into (a plan reuses its activation buffers)."""
+        image = x.dim() == 4
+        if image:
+            assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape[0:1] + x.shape[2:]) == (batch, h, wd), (x.shape, batch, h, wd)
+            assert stride == 1 and not upsample, "stride / upsample belong to the rows input"
+            ldx, cin = 0, x.shape[1]
+        else:
+            assert x.dtype == torch.float16 and x.shape[0] == batch * h * wd and pre in (None, "none"), (x.shape, batch, h, wd, pre)
+            ldx, cin = _rows(x)
+        cout = w.shape[0]
+        assert w.shape == (cout, 9 * cin) and w.dtype == torch.float16 and w.is_contiguous(), (w.shape, w.dtype, cin)
+        assert bias is None or (bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous())
+        if stride == 2 and upsample:
+            raise ValueError("tiny_conv: stride 2 together with upsample is not a form of pv_tiny_conv3x3")
+        hv, wv = (2 * h, 2 * wd) if upsample else (h, wd)
+        ho, wo = (hv - 1) // stride + 1, (wv - 1) // stride + 1
+        m = batch * ho * wo
+        if image_out:
+            assert residual is None and act == ACT_NONE, "the image output has no residual and no activation"
+            if out is None:
+                out = self.empty((batch, cout, ho, wo), torch.float32)
+            assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (batch, cout, ho, wo), (out.shape, batch, cout, ho, wo)
+            ldo = 0
+        else:
+            if out is None:
+                out = self.empty((m, cout))
+            ldo, oc = _rows(out)
+            assert out.dtype == torch.float16 and oc == cout and out.shape[0] == m, (out.shape, m, cout)
+            self.colstats.pop((out.data_ptr(), out.shape[0], cout), None)
+        ldr = 0
+        if residual is not None:
+            ldr, rc = _rows(residual)
+            assert residual.dtype == torch.float16 and rc == cout and residual.shape[0] == m, (residual.shape, m, cout)
+        self.keep.extend((x, w, bias, residual, out))
+        name = "tiny_conv_image_kernel" if image else f"tiny_conv_rows_kernel<{1 if stride == 2 else 4},{1 if image_out else 4},{int(image_out)}>"
+        self._add(self.lib.pv_tiny_conv3x3, _ptr(x), int(image), ldx, TINY_PRE[pre], _ptr(w), _ptr(bias), _ptr(residual), ldr, _ptr(out), int(image_out), ldo,
+                  float(out_scale), float(out_shift), batch, cin, cout, h, wd, int(stride), int(bool(upsample)), int(act),
+                  tag=(name, 2.0 * m * cout * 9 * cin, (4.0 if image else 2.0) * batch * h * wd * cin + (4.0 if image_out else 2.0) * m * cout
+                       + (2.0 * m * cout if residual is not None else 0.0) + 2.0 * cout * 9 * cin))
         return out
 
     def pixel_unshuffle(self, image, *, batch: Optional[int] = None, out=None) -> torch.Tensor:
