@@ -29,6 +29,11 @@ highest-resolution level - every query attends to keys and values pooled ``F`` p
 additional forward), ``--kv_downsample_method avg|nearest`` (block means, the default because it aliases less, or the top-left token) and
 ``--hires_kv_downsample F`` (the factor of the second pass of a ``--hires_latent_size`` run; default the same as ``--kv_downsample``, 1 = off there.
 The intended use: ``--hires_latent_size 96 --hires_kv_downsample 2`` - an exact first pass, a pooled second one).
+
+``--window S`` (windowed denoising, MultiDiffusion: every step denoises the overlapping ``S x S`` windows of the latent canvas as one batch and sets the
+canvas to their weighted mean, so the UNet works at its training size whatever the picture's), ``--window_stride`` (default ``S // 2``),
+``--window_weights uniform|gaussian``, ``--latent_height`` / ``--latent_width`` (a portrait or panorama canvas; default ``--latent_size``, need
+``--window``) and ``--hires_window`` / ``--hires_window_stride`` (the same for the second pass of a ``--hires_latent_size`` run).
 """
 import argparse
 import os
@@ -91,6 +96,15 @@ parser.add_argument("--kv_downsample_layers", nargs="+", type=str, default=None,
                     help="Transformers whose keys / values are pooled: name prefixes as --pag_layers takes them, or all (default: the highest-resolution level)")
 parser.add_argument("--hires_kv_downsample", type=int, default=None,
                     help="The factor in the second pass (with --hires_latent_size; default: --kv_downsample, 1 = off in the second pass)")
+parser.add_argument("--window", type=int, default=None,
+                    help="Windowed denoising (MultiDiffusion): denoise overlapping windows of this latent size and average them (default off)")
+parser.add_argument("--window_stride", type=int, default=None, help="Distance between two windows (default: --window // 2)")
+parser.add_argument("--window_weights", choices=["uniform", "gaussian"], default="uniform",
+                    help="uniform: the plain mean of the windows (MultiDiffusion); gaussian: windows weigh most at their centre (Mixture of Diffusers)")
+parser.add_argument("--hires_window", type=int, default=None, help="Windowed denoising in the second pass (with --hires_latent_size)")
+parser.add_argument("--hires_window_stride", type=int, default=None, help="Distance between two windows of the second pass (default: --hires_window // 2)")
+parser.add_argument("--latent_height", type=int, default=None, help="Height of the latent canvas (default: --latent_size; needs --window)")
+parser.add_argument("--latent_width", type=int, default=None, help="Width of the latent canvas (default: --latent_size; needs --window)")
 parser.add_argument("--vae_tiling", action="store_true",
                     help="vae.enable_tiling(): decode / encode images larger than one tile in overlapping tiles with blended seams (large --hires_latent_size)")
 parser.add_argument("--vae_tile_size", type=int, default=512, help="tile_sample_min_size of --vae_tiling, in pixels")
@@ -168,6 +182,15 @@ def prepare_control(args, unet):
     return cn.to(unet.device), image.clamp(0, 1).contiguous()
 
 
+def canvas_size(args):
+    """The ``latent_size`` of ``run_inference``: ``--latent_size``, or with ``--latent_height`` / ``--latent_width`` the ``(H, W)`` pair of a windowed run."""
+    if args.latent_height is None and args.latent_width is None:
+        return args.latent_size
+    if args.window is None:
+        raise SystemExit("--latent_height / --latent_width need --window: without it the denoiser is one square plan of --latent_size")
+    return (args.latent_size if args.latent_height is None else args.latent_height, args.latent_size if args.latent_width is None else args.latent_width)
+
+
 def configure_vae(args, vae):
     """The VAE switches of the command line (--vae_tiling, --vae_flash_attention): the VAE object carries them into run_inference."""
     if args.vae_tiling:
@@ -225,7 +248,7 @@ if __name__ == "__main__":
     controlnet, control_image = prepare_control(args, unet)
     with torch.no_grad():
         out = run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler, device,
-                            args.encoder_layers_idx, latent_size=args.latent_size, guidance_scale=args.guidance_scale,
+                            args.encoder_layers_idx, latent_size=canvas_size(args), guidance_scale=args.guidance_scale,
                             timesteps=args.num_timesteps, from_noised_image=args.from_noised_image, seed=args.seed,
                             strength=args.strength, inpaint_mask=prepare_mask(args), paste_back=not args.no_paste_back,
                             hires_latent_size=args.hires_latent_size, hires_strength=args.hires_strength, hires_timesteps=args.hires_timesteps,
@@ -235,7 +258,8 @@ if __name__ == "__main__":
                             controlnet_conditioning_scale=args.controlnet_conditioning_scale, kv_downsample=args.kv_downsample,
                             kv_downsample_method=args.kv_downsample_method,
                             kv_downsample_layers=None if args.kv_downsample_layers is None else tuple(args.kv_downsample_layers),
-                            hires_kv_downsample=args.hires_kv_downsample)
+                            hires_kv_downsample=args.hires_kv_downsample, window=args.window, window_stride=args.window_stride,
+                            window_weights=args.window_weights, hires_window=args.hires_window, hires_window_stride=args.hires_window_stride)
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

@@ -746,6 +746,27 @@ int32_t pv_vae_attention(const void* q, const void* k, const void* v, int32_t ld
 int32_t pv_tiny_conv3x3(const void* x, int32_t x_is_image, int32_t ldx, int32_t pre, const void* w, const float* bias, const void* res, int32_t ldr,
                         void* out, int32_t out_is_image, int32_t ldo, float out_scale, float out_shift, int32_t batch, int32_t cin, int32_t cout, int32_t h,
                         int32_t wd, int32_t stride, int32_t upsample, int32_t act, void* stream);
+/* (ABI 19, symbols added) [EXT] pv_window_gather / pv_window_blend: the two launches of windowed denoising (MultiDiffusion, Bar-Tal et al. 2023; diffusers'
+ * StableDiffusionPanoramaPipeline; pv_window.hip), bound through _lib.EXT_SIGNATURES.  Both tensors fp32 NCHW, contiguous:
+ *   canvas  [batch][channels][H][W]                    windows [batch*ny*nx][channels][S][S]
+ * Window k = ky*nx + kx of sample b is row b*ny*nx + k of windows and covers canvas rows oy[ky] ... oy[ky]+S-1, columns ox[kx] ... ox[kx]+S-1.
+ * oy[ny] and ox[nx] are HOST arrays: they are read during the call and reach the kernel by value, so nothing has to outlive the call, the launch can be
+ * captured, and every check below runs before the first HIP call.
+ *   pv_window_gather:  windows[b*ny*nx + k][c][y][x] = canvas[b][c][oy[ky] + y][ox[kx] + x]                       a copy, bit for bit
+ *   pv_window_blend:   canvas[b][c][y][x] = num / den, in fp32, with the sums over the windows that cover (y, x), ky outer and kx inner, ascending:
+ *                        num = sum_ky sum_kx (profile[y - oy[ky]] * profile[x - ox[kx]]) * windows[b*ny*nx + k][c][y - oy[ky]][x - ox[kx]]
+ *                        den = (sum_ky profile[y - oy[ky]]) * (sum_kx profile[x - ox[kx]])
+ *                      profile: device fp32 [S], strictly positive; NULL: all ones.  A sum starts with its first term (no 0 + ...), so an element that
+ *                      one window covers, under a NULL profile, keeps that window's bits.
+ * Every lane owns its output elements: no atomics, no LDS, no scratch, a fixed summation order - every launch gives the same bits.  16-byte loads and stores
+ * where all pointers are 16-byte aligned and W, S and every ox are multiples of 4; a scalar path for everything else.
+ * canvas, windows, oy, ox non-null; pointers 4-byte aligned; batch, channels >= 1; 1 <= ny, nx <= 64; 1 <= S <= min(H, W); per axis o[0] == 0, the origins
+ * strictly increasing and at most S apart (every element is covered), o[last] + S == the extent; both tensors below 2^29 elements; windows and canvas do
+ * not overlap (nor does profile overlap either).  Anything else returns hipErrorInvalidValue before any HIP call. */
+int32_t pv_window_gather(const float* canvas, float* windows, int32_t batch, int32_t channels, int32_t H, int32_t W, int32_t S, const int32_t* oy,
+                         int32_t ny, const int32_t* ox, int32_t nx, void* stream);
+int32_t pv_window_blend(const float* windows, const float* profile, float* canvas, int32_t batch, int32_t channels, int32_t H, int32_t W, int32_t S,
+                        const int32_t* oy, int32_t ny, const int32_t* ox, int32_t nx, void* stream);
 /* vae.encode(x).latent_dist.sample() (infer.py:63, train.py:473): moments fp32 [B][2c][hw] (mean | logvar, NCHW),
  * out = mean + exp(0.5*clamp(logvar,-30,20)) * eps */
 int pv_posterior_sample(const float* moments, const float* eps, float* out, int32_t batch, int64_t chw, void* stream);

@@ -10,4 +10,7 @@ def __getattr__(name):           # lazy: importing the package stays free of tor
     if name == "AutoencoderTiny":
         from .vae_tiny import AutoencoderTiny
         return AutoencoderTiny
+    if name in ("WindowedDenoiseLoop", "window_origins", "window_profile"):
+        from . import multidiffusion
+        return getattr(multidiffusion, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

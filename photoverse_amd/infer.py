@@ -39,6 +39,11 @@ zero-conv residuals to the UNet's skip connections and mid block output (``UNetE
 And token downsampling ([EXT] ToDo, Smith et al. 2024): ``kv_downsample`` / ``hires_kv_downsample`` pool the keys and values of the chosen self-attention
 layers by a factor per side (``pv_token_pool``, one launch behind the layer's qkv projection) while every query still attends: the N^2 part of the
 high-resolution levels shrinks by the factor squared, approximately, with no weights changed.
+
+And windowed denoising ([EXT] MultiDiffusion, Bar-Tal et al. 2023; diffusers' ``StableDiffusionPanoramaPipeline``): with ``window`` / ``hires_window`` a pass
+runs through a ``multidiffusion.WindowedDenoiseLoop`` - every step denoises overlapping windows of the training size as samples of a larger batch on the
+ordinary cached ``DenoiseLoop`` and sets the canvas to their weighted mean (``pv_window_gather`` / ``pv_window_blend`` around the step) - so the canvas may
+have any height and width.
 """
 from __future__ import annotations
 
@@ -48,6 +53,7 @@ from collections import OrderedDict
 
 import torch
 
+from .multidiffusion import WINDOW_WEIGHTS, WindowedDenoiseLoop, window_grid
 from .pipeline import DenoiseLoop
 from .scheduler import DPMSolverMultistepScheduler
 from .unet import KV_DOWNSAMPLE_METHODS, check_kv_downsample_factor, normalize_freeu, resolve_kv_downsample_layers, resolve_pag_layers
@@ -144,12 +150,23 @@ def _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, traini
     return loop
 
 
+def _pass_loop(grid, weights, unet, batch, latent_size, n_ip, steps, guidance, scheduler, **kw):
+    """The loop of one pass: the cached ``DenoiseLoop`` itself (``grid`` None), or a ``WindowedDenoiseLoop`` over ``grid`` (``window_grid``'s tuple) around
+    the cached ``DenoiseLoop`` of batch ``batch * nW`` at the window size - the same cache, keys and eviction."""
+    if grid is None:
+        return _loop_for(unet, batch, latent_size, n_ip, steps, guidance, scheduler, **kw)
+    H, W, S, stride, oy, ox = grid
+    inner = _loop_for(unet, batch * len(oy) * len(ox), S, n_ip, steps, guidance, scheduler, **kw)
+    return WindowedDenoiseLoop(unet, batch, (H, W), S, n_ip, steps, guidance, window_stride=stride, window_weights=weights, inner=inner)
+
+
 def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_adapter, image_adapter, vae, scheduler,
                   device, image_encoder_layers_idx, latent_size=64, guidance_scale=1, timesteps=100, token_index=0,
                   disable_tqdm=False, seed=None, from_noised_image=False, training_mode=False, *, noise=None, strength=1.0,
                   image_guidance_scale=None, guidance_rescale=0.0, sampler="dpmsolver++", sample_offset=0, pag_scale=None, pag_layers=("mid_block",),
                   freeu=None, controlnet=None, control_image=None, controlnet_conditioning_scale=1.0, kv_downsample=None,
-                  kv_downsample_method="avg", kv_downsample_layers=None, hires_kv_downsample=None, inpaint_mask=None, paste_back=True,
+                  kv_downsample_method="avg", kv_downsample_layers=None, hires_kv_downsample=None, window=None, window_stride=None,
+                  window_weights="uniform", hires_window=None, hires_window_stride=None, inpaint_mask=None, paste_back=True,
                   hires_latent_size=None, hires_strength=0.5, hires_timesteps=None, hires_noise=None):
     """Same 11 positional + 8 keyword arguments as the reference.  ``noise`` (keyword-only, new): a caller-drawn start noise
     ``(B, C, latent, latent)`` replacing the draw of ``infer.py:52-59`` - used by the batch-sharded pipeline, which draws the
@@ -209,7 +226,49 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
     highest-resolution level, first down block and last up block, where the token count is largest - or name prefixes / ``"all"`` as ``pag_layers``
     takes them; an entry that selects nothing is a ``ValueError``.  ``hires_kv_downsample`` (needs ``hires_latent_size``): the factor of the second pass -
     None: the same as ``kv_downsample``; 1: off in the second pass; else an int in 2 ... 8.  The intended use is an exact first pass and a pooled second
-    one, where self-attention dominates: ``kv_downsample=None, hires_kv_downsample=2``.  Combines with every keyword above except ``training_mode``."""
+    one, where self-attention dominates: ``kv_downsample=None, hires_kv_downsample=2``.  Combines with every keyword above except ``training_mode``.
+
+    ``window`` (None: off) / ``window_stride`` (None: ``window // 2``) / ``window_weights`` (``"uniform"``, ``"gaussian"``): windowed denoising
+    (MultiDiffusion).  The first pass runs on a canvas of ``latent_size`` - then an int or an ``(H, W)`` pair, each side at least ``window`` - whose every
+    step denoises the overlapping ``window x window`` crops (origins ``multidiffusion.window_origins``) as one batch, each with its own solver state,
+    and sets the canvas to their weighted mean: the UNet works at the size it was trained at whatever the picture's size and aspect.  Every guidance,
+    ``freeu``, ``kv_downsample``, ``controlnet`` and ``inpaint_mask`` keyword acts per window.  A rectangular canvas does not combine with
+    ``inpaint_mask``, ``from_noised_image``, ``controlnet`` or ``hires_latent_size`` yet.  ``hires_window`` / ``hires_window_stride`` (need
+    ``hires_latent_size``): the same for the second pass, which uses the same ``window_weights`` - there is one weights argument for both passes.  A pair
+    as ``latent_size`` does not work through ``PhotoVersePipeline(..., shard=True, seed=...)``: that call draws the global batch's noise for a square
+    ``latent_size`` before this function runs, so a sharded seeded call takes an int (a square canvas, windowed or not).  Neither window combines with ``sampler="sde-dpmsolver++"`` (the windows' fresh noise would
+    be averaged in the overlaps) or ``training_mode``.  With both None the call is what it was: same launches, same bits."""
+    grid1 = grid2 = None                                                                    # before any model is touched
+    if window_weights not in WINDOW_WEIGHTS:
+        raise ValueError(f"window_weights must be one of {WINDOW_WEIGHTS}, got {window_weights!r}")
+    if window is None:
+        if window_stride is not None:
+            raise ValueError("window_stride needs window")
+        if not isinstance(latent_size, numbers.Integral):
+            raise ValueError(f"latent_size {latent_size!r} needs window: without it the canvas is one square plan and latent_size an int")
+    else:
+        grid1 = window_grid(latent_size, window, window_stride)
+        if grid1[0] == grid1[1]:
+            latent_size = grid1[0]
+        else:
+            for name, given in (("inpaint_mask", inpaint_mask is not None), ("from_noised_image", bool(from_noised_image)),
+                                ("controlnet", controlnet is not None or control_image is not None), ("hires_latent_size", hires_latent_size is not None)):
+                if given:
+                    raise ValueError(f"a rectangular canvas ({grid1[0]} x {grid1[1]}) does not combine with {name} yet")
+    if hires_window is None:
+        if hires_window_stride is not None:
+            raise ValueError("hires_window_stride needs hires_window")
+    else:
+        if hires_latent_size is None:
+            raise ValueError("hires_window needs hires_latent_size")
+        if not _is_positive_int(hires_latent_size):
+            raise ValueError(f"hires_latent_size must be a positive int, got {hires_latent_size!r}")
+        grid2 = window_grid(hires_latent_size, hires_window, hires_window_stride)
+    if grid1 is not None or grid2 is not None:
+        if sampler == "sde-dpmsolver++":
+            raise ValueError("window / hires_window do not combine with sampler='sde-dpmsolver++': the windows' noise would be averaged in the overlaps")
+        if training_mode:
+            raise ValueError("window / hires_window do not combine with training_mode=True")
     if kv_downsample is not None:                                                           # before any model is touched
         check_kv_downsample_factor(kv_downsample, "kv_downsample")
     if hires_kv_downsample is not None:
@@ -310,7 +369,7 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         uncond_input_ids = tokenizer([""] * batch, padding="max_length", max_length=tokenizer.model_max_length,
                                      return_tensors="pt").input_ids
 
-    shape = (batch, unet.config.in_channels, latent_size, latent_size)                    # :52-59 noise on CPU, then moved
+    shape = (batch, unet.config.in_channels) + ((latent_size, latent_size) if grid1 is None else grid1[:2])     # :52-59 noise on CPU, then moved
     generator = None
     if noise is not None:
         if tuple(noise.shape) != shape:
@@ -372,9 +431,9 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
                                           "concept_text_embeddings": concept_text_embeddings,
                                           "concept_placeholder_idx": placeholder_idx})[0]
 
-    loop = _loop_for(unet, batch, latent_size, encoder_hidden_states_image.shape[1], timesteps, guidance_scale, sch,     # :98-119
-                     training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint, **guide,
-                     controlnet=controlnet, conditioning_scale=float(controlnet_conditioning_scale), kv_downsample=kv_pass1)
+    loop = _pass_loop(grid1, window_weights, unet, batch, latent_size, encoder_hidden_states_image.shape[1], timesteps, guidance_scale, sch,     # :98-119
+                      training_mode=training_mode, fusion_seed=0 if seed is None else int(seed), inpaint=inpaint, **guide,
+                      controlnet=controlnet, conditioning_scale=float(controlnet_conditioning_scale), kv_downsample=kv_pass1)
     loop.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
     if controlnet is not None:
         loop.set_control(control_image)
@@ -389,8 +448,8 @@ def run_inference(example, tokenizer, image_encoder, text_encoder, unet, text_ad
         # second pass: upscale + re-noise in one launch, then the tail of a fresh schedule at the large size under the same conditioning
         sch2 = _scheduler_for(scheduler, sampler)
         x_start, start2 = hires_start(latents, hires_noise.to(device), sch2, hires_steps, hires_strength)
-        loop2 = _loop_for(unet, batch, hires_latent_size, encoder_hidden_states_image.shape[1], hires_steps, guidance_scale, sch2,
-                          fusion_seed=0 if seed is None else int(seed), **guide, kv_downsample=kv_pass2)
+        loop2 = _pass_loop(grid2, window_weights, unet, batch, hires_latent_size, encoder_hidden_states_image.shape[1], hires_steps, guidance_scale, sch2,
+                           fusion_seed=0 if seed is None else int(seed), **guide, kv_downsample=kv_pass2)
         loop2.set_conditioning((encoder_hidden_states, encoder_hidden_states_image), (uncond_embeddings, uncond_encoder_hidden_states_image))
         if stochastic:
             loop2.set_noise_stream(noise_seed, int(sample_offset), stream=1)

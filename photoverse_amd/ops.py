@@ -1256,3 +1256,49 @@ def tile_blend(tile, above, left, out, *, ev: int, eh: int, keep_h: int, keep_w:
                                    out.shape[2], out.shape[3], int(oy), int(ox), torch.cuda.current_stream(tile.device).cuda_stream)
     if rc != 0:
         raise HipLaunchError(f"pv_tile_blend failed with hipError {rc}")
+
+
+def _window_args(S, oy, ox):
+    """(S, oy array, ny, ox array, nx) for the window launchers: the origins as host int32 arrays, read during the call."""
+    import ctypes
+    oy, ox = tuple(int(v) for v in oy), tuple(int(v) for v in ox)
+    return int(S), (ctypes.c_int * len(oy))(*oy), len(oy), (ctypes.c_int * len(ox))(*ox), len(ox)
+
+
+def _window_operand(t, what, shape=None):
+    require_cuda(t, what)
+    assert t.dtype == torch.float32 and t.is_contiguous() and (shape is None or tuple(t.shape) == tuple(shape)), (what, t.dtype, tuple(t.shape), shape)
+
+
+def window_gather(canvas, S, oy, ox, out=None):
+    """[EXT] The overlapping ``S x S`` windows of a canvas (``pv_window_gather``), launched on the current stream: ``canvas`` fp32 (B, C, H, W) ->
+    (B * ny * nx, C, S, S), window ``k = ky * nx + kx`` of sample ``b`` in row ``b * ny * nx + k``, holding ``canvas[b, :, oy[ky]:oy[ky] + S,
+    ox[kx]:ox[kx] + S]`` bit for bit.  ``oy`` / ``ox``: host ints as ``multidiffusion.window_origins`` gives them.  ``out``: the window tensor to fill."""
+    _window_operand(canvas, "window_gather canvas")
+    B, ch, H, W = canvas.shape
+    S, a_oy, ny, a_ox, nx = _window_args(S, oy, ox)
+    shape = (B * ny * nx, ch, S, S)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=canvas.device)
+    _window_operand(out, "window_gather out", shape)
+    rc = _lib.load().pv_window_gather(_ptr(canvas), _ptr(out), B, ch, H, W, S, a_oy, ny, a_ox, nx, torch.cuda.current_stream(canvas.device).cuda_stream)
+    if rc != 0:
+        raise HipLaunchError(f"pv_window_gather failed with hipError {rc}")
+    return out
+
+
+def window_blend(windows, canvas, S, oy, ox, profile=None):
+    """[EXT] The canvas as the weighted mean of its windows (``pv_window_blend``), launched on the current stream: every element of ``canvas`` fp32
+    (B, C, H, W) becomes ``sum_k w_k * windows_k / sum_k w_k`` over the windows of ``windows`` (B * ny * nx, C, S, S; the layout of ``window_gather``) that
+    cover it, ``w = profile[y - oy] * profile[x - ox]`` with ``profile`` a strictly positive device fp32 ``[S]`` (None: ones - the plain mean)."""
+    _window_operand(canvas, "window_blend canvas")
+    B, ch, H, W = canvas.shape
+    S, a_oy, ny, a_ox, nx = _window_args(S, oy, ox)
+    _window_operand(windows, "window_blend windows", (B * ny * nx, ch, S, S))
+    if profile is not None:
+        _window_operand(profile, "window_blend profile", (S,))
+    rc = _lib.load().pv_window_blend(_ptr(windows), _ptr(profile), _ptr(canvas), B, ch, H, W, S, a_oy, ny, a_ox, nx,
+                                     torch.cuda.current_stream(canvas.device).cuda_stream)
+    if rc != 0:
+        raise HipLaunchError(f"pv_window_blend failed with hipError {rc}")
+    return canvas
