@@ -34,6 +34,10 @@ The intended use: ``--hires_latent_size 96 --hires_kv_downsample 2`` - an exact 
 canvas to their weighted mean, so the UNet works at its training size whatever the picture's), ``--window_stride`` (default ``S // 2``),
 ``--window_weights uniform|gaussian``, ``--latent_height`` / ``--latent_width`` (a portrait or panorama canvas; default ``--latent_size``, need
 ``--window``) and ``--hires_window`` / ``--hires_window_stride`` (the same for the second pass of a ``--hires_latent_size`` run).
+
+``--upscaler_path FILE|random`` (Real-ESRGAN's RRDBNet, ``RealESRGAN_x4plus.pth``: the images ``run_inference`` returns are upscaled 4x before they are saved -
+it runs after the call, so it composes with every flag above), ``--upscaler_blocks`` (the size of the ``random`` network; 23 is x4plus), ``--upscale_tile``
+and ``--upscale_tile_pad`` (Real-ESRGAN's tiling: input tiles with a margin of real neighbourhood, cropped without blending).
 """
 import argparse
 import os
@@ -113,6 +117,13 @@ parser.add_argument("--vae_flash_attention", action="store_true",
                     help="vae.enable_flash_attention(): the VAE mid-block attention as one flash launch with no score matrix (untiled decode of large latents)")
 parser.add_argument("--vae_tiny_path", type=str, default=None,
                     help="AutoencoderTiny (TAESD) directory, or 'random' for seeded random weights: the tiny autoencoder replaces the VAE in run_inference")
+parser.add_argument("--upscaler_path", type=str, default=None,
+                    help="Real-ESRGAN RRDBNet weights (RealESRGAN_x4plus.pth or a .safetensors of the same names), or 'random' for seeded random weights: "
+                         "the generated images are upscaled 4x before they are saved")
+parser.add_argument("--upscaler_blocks", type=int, default=None, help="RRDB blocks of --upscaler_path random (default 23, the x4plus size; a file brings its own)")
+parser.add_argument("--upscale_tile", type=int, default=None,
+                    help="Upscale in tiles of this many input pixels per side (Real-ESRGAN's tile; default: the whole image where it fits)")
+parser.add_argument("--upscale_tile_pad", type=int, default=10, help="Pixels of real neighbourhood around every tile of --upscale_tile, cropped from its output")
 parser.add_argument("--tiny", action="store_true", help="Small random-init model (smoke tests of the CLI; needs --model_path random)")
 
 
@@ -224,8 +235,50 @@ def select_vae(args, vae, device):
     return configure_vae(args, vae) if tiny is None else tiny
 
 
+def check_upscaler_args(args):
+    """The ``--upscaler_path`` / ``--upscale_*`` flags, checked before any model is loaded: a bad value exits with a message."""
+    if args.upscaler_path is None:
+        for flag in ("upscaler_blocks", "upscale_tile"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} needs --upscaler_path")
+        return
+    if args.upscaler_path == "random":
+        if args.upscaler_blocks is not None and args.upscaler_blocks < 1:
+            raise SystemExit(f"--upscaler_blocks must be >= 1, got {args.upscaler_blocks}")
+    else:
+        if args.upscaler_blocks is not None:
+            raise SystemExit("--upscaler_blocks belongs to --upscaler_path random: a weight file brings its own block count")
+        if not os.path.isfile(args.upscaler_path):
+            raise SystemExit(f"--upscaler_path: no file at {args.upscaler_path}")
+    if args.upscale_tile is not None and args.upscale_tile < 1:
+        raise SystemExit(f"--upscale_tile must be >= 1, got {args.upscale_tile}")
+    if args.upscale_tile_pad < 0:
+        raise SystemExit(f"--upscale_tile_pad must be >= 0, got {args.upscale_tile_pad}")
+
+
+def prepare_upscaler(args, device):
+    """``--upscaler_path`` -> an ``RRDBNet`` on ``device``, or None."""
+    check_upscaler_args(args)
+    if args.upscaler_path is None:
+        return None
+    from photoverse_amd.upscaler import RRDBNet
+    if args.upscaler_path == "random":
+        net = RRDBNet(num_block=23 if args.upscaler_blocks is None else args.upscaler_blocks).randomize_(seed=0 if args.seed is None else args.seed)
+    else:
+        net = RRDBNet.from_pretrained(args.upscaler_path)
+    return net.requires_grad_(False).to(device)
+
+
+def upscale_images(args, upscaler, images):
+    """The images ``run_inference`` returned, 4x larger through ``--upscaler_path`` (unchanged without it)."""
+    if upscaler is None:
+        return images
+    return upscaler.upscale(images.float(), tile=args.upscale_tile, tile_pad=args.upscale_tile_pad)
+
+
 if __name__ == "__main__":
     args = parser.parse_args()
+    check_upscaler_args(args)
     if not torch.cuda.is_available():
         raise SystemExit("generate.py needs a HIP device: photoverse_amd has no CPU path")
     device = torch.device("cuda")
@@ -260,6 +313,7 @@ if __name__ == "__main__":
                             kv_downsample_layers=None if args.kv_downsample_layers is None else tuple(args.kv_downsample_layers),
                             hires_kv_downsample=args.hires_kv_downsample, window=args.window, window_stride=args.window_stride,
                             window_weights=args.window_weights, hires_window=args.hires_window, hires_window_stride=args.hires_window_stride)
+        out = upscale_images(args, prepare_upscaler(args, device), out)
     os.makedirs(args.results_dir, exist_ok=True)
     from photoverse_amd.image_utils import denormalize, to_pil
     imgs = [to_pil(denormalize(img)) for img in out.float().cpu()]                            # generate.py:86

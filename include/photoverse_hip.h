@@ -746,6 +746,30 @@ int32_t pv_vae_attention(const void* q, const void* k, const void* v, int32_t ld
 int32_t pv_tiny_conv3x3(const void* x, int32_t x_is_image, int32_t ldx, int32_t pre, const void* w, const float* bias, const void* res, int32_t ldr,
                         void* out, int32_t out_is_image, int32_t ldo, float out_scale, float out_shift, int32_t batch, int32_t cin, int32_t cout, int32_t h,
                         int32_t wd, int32_t stride, int32_t upsample, int32_t act, void* stream);
+/* (ABI 19, symbols added) [EXT] pv_dense_conv3x3: the 3x3 convs (pad 1, stride 1) of an RRDBNet - Real-ESRGAN's RealESRGAN_x4plus super-resolution model
+ * (Wang et al. 2021; basicsr's RRDBNet; pv_denseconv.hip), bound through _lib.EXT_SIGNATURES.  x: fp16 rows [batch*h*wd][>= cin], leading dimension ldx;
+ * ONLY the columns [0, cin) of a row are read.
+ *   y   = bias[co] (0 if bias == NULL) + sum_{ky,kx,ci} X[b][iy][ix][ci] * w[co][(ky*3 + kx)*cin + ci]     w: fp16 [cout][9*cin], tap-major (as pv_tiny_conv3x3)
+ *   a   = act(y)                      act = PV_ACT_NONE or PV_ACT_LEAKY_RELU: y > 0 ? y : slope * y (slope: a float argument, not the 0.01 of the other launchers)
+ *   o   = alpha * a + res[row][co]    if res  != NULL (fp16 rows, leading dimension ldr), else a
+ *   o   = beta  * o + res2[row][co]   if res2 != NULL (fp16 rows, leading dimension ldr2); res2 needs res
+ *   out[row][co] = fp16(o)            ONE rounding; fp32 before it (each scaled residual is one fma), a fixed accumulation order
+ * cin in {64, 96, 128, 160, 192}; cout in {32, 64}.  upsample 0 or 1: with 1 the conv sees the 2h x 2wd nearest-neighbour upsampling - tap (iy, ix) reads
+ * row (iy >> 1, ix >> 1), the zero padding lies outside [0, 2h) x [0, 2wd), the upsampled tensor is never written, out has batch*2h*2wd rows - and
+ * cin == cout == 64.
+ * THE IN-PLACE DENSE BLOCK.  out may be a column slice of the buffer x lives in: the same rows (ldo == ldx), the columns [c_off, c_off + cout) with
+ * c_off >= cin and c_off + cout <= ldx.  The launch reads nothing at or beyond column cin of any row - no 16-byte access of x reaches past column cin - and
+ * writes nothing outside out[row][0 .. cout).  res and res2 overlap neither out nor each other, in elements: either may be a column slice of the rows out
+ * or x lives in, e.g. x's own columns [0, 64).  So a ResidualDenseBlock needs no concatenation: one [rows][192] buffer, conv1 .. conv4 writing the columns
+ * 64-95, 96-127, 128-159, 160-191 with LeakyReLU, conv5 reading all 192 and writing the next block's buffer with alpha = 0.2, res = x; the third block's
+ * conv5 carries the RRDB's outer residual as beta = 0.2, res2 = the RRDB's input: two residuals, one rounding.
+ * No atomics, no scratch buffer; every launch gives the same bits, and a batch gives the bits of its images launched one by one (no tap crosses into a
+ * neighbouring image's rows; rows behind the last image are never read).  Safe under stream capture.  Pointers 16-byte aligned; ldx, ldo, ldr, ldr2
+ * multiples of 8 and >= the width read or written; every extent below 2 GiB; batch, h, wd >= 1; slope, alpha, beta finite; out overlaps neither w nor
+ * bias.  Anything else returns hipErrorInvalidValue before any HIP call. */
+int32_t pv_dense_conv3x3(const void* x, int32_t ldx, const void* w, const float* bias, const void* res, int32_t ldr, const void* res2, int32_t ldr2,
+                         void* out, int32_t ldo, int32_t batch, int32_t cin, int32_t cout, int32_t h, int32_t wd, int32_t upsample, int32_t act,
+                         float slope, float alpha, float beta, void* stream);
 /* (ABI 19, symbols added) [EXT] pv_window_gather / pv_window_blend: the two launches of windowed denoising (MultiDiffusion, Bar-Tal et al. 2023; diffusers'
  * StableDiffusionPanoramaPipeline; pv_window.hip), bound through _lib.EXT_SIGNATURES.  Both tensors fp32 NCHW, contiguous:
  *   canvas  [batch][channels][H][W]                    windows [batch*ny*nx][channels][S][S]

@@ -10,6 +10,9 @@ def __getattr__(name):           # lazy: importing the package stays free of tor
     if name == "AutoencoderTiny":
         from .vae_tiny import AutoencoderTiny
         return AutoencoderTiny
+    if name == "RRDBNet":
+        from .upscaler import RRDBNet
+        return RRDBNet
     if name in ("WindowedDenoiseLoop", "window_origins", "window_profile"):
         from . import multidiffusion
         return getattr(multidiffusion, name)

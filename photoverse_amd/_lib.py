@@ -202,6 +202,8 @@ EXT_SIGNATURES = {
     "pv_vae_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     # the 3x3 convs of AutoencoderTiny (``tests/test_vae_tiny_gpu.py``)
     "pv_tiny_conv3x3": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float] + [c_int] * 8 + [c_void_p]),
+    # the 3x3 convs of RRDBNet, the Real-ESRGAN upscaler (``tests/test_upscaler_gpu.py``)
+    "pv_dense_conv3x3": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 8 + [c_float] * 3 + [c_void_p]),
     # the two launches of windowed denoising (``tests/test_multidiffusion_gpu.py``); the origins are host int32 arrays
     "pv_window_gather": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [C.POINTER(c_int), c_int, C.POINTER(c_int), c_int, c_void_p]),
     "pv_window_blend": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [C.POINTER(c_int), c_int, C.POINTER(c_int), c_int, c_void_p]),

@@ -1000,6 +1000,43 @@ class Recorder:
                        + (2.0 * m * cout if residual is not None else 0.0) + 2.0 * cout * 9 * cin))
         return out
 
+    def dense_conv(self, x, w, bias=None, *, batch: int, h: int, wd: int, cin: Optional[int] = None, upsample: bool = False, act: int = ACT_NONE,
+                   slope: float = 0.2, residual=None, alpha: float = 1.0, residual2=None, beta: float = 1.0, out=None):
+        """[EXT] One 3x3 conv (pad 1, stride 1) of an ``RRDBNet`` (``pv_dense_conv3x3``).  ``x``: fp16 rows ``[batch * h * wd][>= cin]`` (a 2-D row view);
+        only its first ``cin`` columns are read (default: all of the view's), ``cin`` in 64 / 96 / 128 / 160 / 192.  ``w``: fp16 ``[cout][9 * cin]``,
+        tap-major, ``cout`` 32 / 64; ``bias``: fp32 ``[cout]`` or None.  -> fp16 rows = ``beta * (alpha * act(conv + bias) + residual) + residual2``, one
+        rounding (``act`` ACT_NONE / ACT_LEAKY_RELU with ``slope``; ``residual2`` needs ``residual``).  ``upsample``: the conv of the nearest-x2 upsampled
+        input (64 -> 64 only), which is never written.  ``out=``: the rows to write - also a column slice of ``x``'s own buffer at or behind column
+        ``cin`` (the in-place dense block: no concatenation)."""
+        assert x.dim() == 2 and x.dtype == torch.float16 and x.shape[0] == batch * h * wd, (x.shape, x.dtype, batch, h, wd)
+        ldx, xc = _rows(x)
+        cin = xc if cin is None else int(cin)
+        assert cin <= xc, (cin, xc)
+        cout = w.shape[0]
+        assert w.shape == (cout, 9 * cin) and w.dtype == torch.float16 and w.is_contiguous(), (w.shape, w.dtype, cin)
+        assert bias is None or (bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous())
+        m = batch * h * wd * (4 if upsample else 1)
+        if out is None:
+            out = self.empty((m, cout))
+        ldo, oc = _rows(out)
+        assert out.dtype == torch.float16 and oc == cout and out.shape[0] == m, (out.shape, m, cout)
+        self.colstats.pop((out.data_ptr(), out.shape[0], cout), None)
+        ldr = ldr2 = 0
+        if residual is not None:
+            ldr, rc = _rows(residual)
+            assert residual.dtype == torch.float16 and rc == cout and residual.shape[0] == m, (residual.shape, m, cout)
+        if residual2 is not None:
+            assert residual is not None, "residual2 needs residual"
+            ldr2, rc = _rows(residual2)
+            assert residual2.dtype == torch.float16 and rc == cout and residual2.shape[0] == m, (residual2.shape, m, cout)
+        self.keep.extend((x, w, bias, residual, residual2, out))
+        nres = (residual is not None) + (residual2 is not None)
+        self._add(self.lib.pv_dense_conv3x3, _ptr(x), ldx, _ptr(w), _ptr(bias), _ptr(residual), ldr, _ptr(residual2), ldr2, _ptr(out), ldo, batch, cin, cout,
+                  h, wd, int(bool(upsample)), int(act), float(slope), float(alpha), float(beta),
+                  tag=(f"dense_conv_kernel<{cout // 16},{int(bool(upsample))}>", 2.0 * m * cout * 9 * cin,
+                       2.0 * batch * h * wd * cin + 2.0 * m * cout * (1 + nres) + 2.0 * cout * 9 * cin))
+        return out
+
     def pixel_unshuffle(self, image, *, batch: Optional[int] = None, out=None) -> torch.Tensor:
         """[EXT] ``PixelUnshuffle(8)`` of an fp32 NCHW image (B, C <= 4, H, W), H and W multiples of 8, into fp16 rows ``[batch * (H / 8) * (W / 8)][64 C]``
         (``pv_pixel_unshuffle8``): column ``c * 64 + i * 8 + j`` of pixel (y, x) is ``image[b][c][8 y + i][8 x + j]``, rounded to fp16 - the first layer of a
